@@ -22,6 +22,11 @@ with dynamic loss scaling). Default window: 20 timed steps after 5 warm-up steps
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp32|bf16|fp16] [--global_envs G | --weak | --envs E]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
+A plain run does only what the headline figure needs: set up, warm up, time the steps, print the
+result line. --dump-outputs DIR also writes what the last timed step computed (dump_outputs
+below). --full adds everything else the benchmark can measure, after the timed steps (today the
+per-phase timings of --phases).
+
 `python bench.py --gpus N` without a launcher starts the N ranks itself (parallel/launch.py): one
 process per GPU, rank r on device r, over RCCL; it fails before any work if fewer than N devices
 are visible (MACBF_DP_BACKEND=gloo rehearses N ranks on one device) or if a launcher's
@@ -71,6 +76,12 @@ def main():
                     help="replay each iteration as captured HIP graphs (launch-bound small configs)")
     ap.add_argument("--phases", action="store_true",
                     help="after the timed loop, 2 extra steps with per-phase device-event timings")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: today the per-phase timings of --phases. A plain "
+                         "run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(see dump_outputs)")
     ap.add_argument("--device", default="hip", choices=["hip", "cpu"],
                     help="cpu: the pure-torch oracle engine over gloo (launch-path rehearsal and CPU tests; "
                          "not a benchmark)")
@@ -130,8 +141,10 @@ def main():
                        dtype=torch.float64, device=dev).sum(0)    # agent_steps, safe_agents, T
     dp.all_reduce_(acc)
     agent_steps, safe_agents, t_sum = acc.tolist()
+    if args.dump_outputs and rank == 0:      # before any extra step moves the parameters on
+        dump_outputs(args.dump_outputs, tr, stats[-1] if stats else None)
     phases = None
-    if args.phases:          # outside the timed region
+    if args.phases or args.full:          # outside the timed region
         tr.timer.enabled = True
         tot = {}
         for _ in range(2):
@@ -183,6 +196,29 @@ def main():
     if rank == 0:
         print(json.dumps(out), flush=True)
     dp.shutdown()
+
+
+DUMP_STATS = ["loss_total", "loss_dang", "loss_safe", "loss_dang_deriv", "loss_safe_deriv", "loss_action",
+              "acc_dang_sum", "acc_safe_sum", "acc_dang_deriv_sum", "acc_safe_deriv_sum",
+              "n_dang", "n_safe", "agent_steps", "safe_agents", "T"]
+
+
+def dump_outputs(path, tr, stats):
+    """--dump-outputs: what a caller of ``train_step`` holds after the last timed step (rank 0's),
+    one .npy each. The inputs depend only on the arguments (seeded weights, scenarios keyed by
+    seed, iteration and rank), so two builds run with the same arguments compare file for file.
+
+    params.npy  float32 (P,)   the flat parameters after the step's Adam update (P = 51141 at --dim 2)
+    grad.npy    float32 (P,)   the step's flat gradient (all-reduced over the ranks)
+    stats.npy   float64 (15,)  the step's statistics, in the order of DUMP_STATS
+    """
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "params.npy"), tr.fp.flat.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "grad.npy"), tr.fp.grad.detach().float().cpu().numpy())
+    if stats is not None:
+        np.save(os.path.join(path, "stats.npy"),
+                np.array([float(stats.get(k, float("nan"))) for k in DUMP_STATS], dtype=np.float64))
 
 
 def _device_uid(torch, dev) -> int:

@@ -128,3 +128,37 @@ def test_bench_gpus2_gloo_rehearsal_on_one_device():
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["world"] == 2 and out["dp_backend"] == "gloo"
     assert out["shared_devices"] and len(out["device_ids"]) == 2
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """--dump-outputs writes what train_step left after warmup + steps iterations. The same
+    iterations run here on one trainer (one code path, one seed: only the order of float
+    accumulation may differ) give the same gradient within the bound of the fp32 gradient tests,
+    and parameters at least 10x closer to the dump than those one Adam step earlier."""
+    import numpy as np
+    from macbf_gnn_amd.engine import Trainer
+    r = _bench(["--gpus", "1", "--agents", "64", "--envs", "2", "--steps", "2", "--warmup", "1", "--inner_loops", "8",
+                "--dump-outputs", str(tmp_path)], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    got = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ["grad", "params", "stats"]
+    assert got["params"].dtype == got["grad"].dtype == np.float32 and got["stats"].dtype == np.float64
+    tr = Trainer(C.TrainConfig(num_agents=64, num_envs=2, inner_loops=8, seed=0, device="hip",
+                               display_steps=10 ** 9, save_steps=10 ** 9))
+    for _ in range(2):
+        tr.train_step()
+    before = tr.fp.flat.double().cpu().numpy()
+    st = tr.train_step()
+    torch.cuda.synchronize()
+    rel = lambda a, b: float(np.linalg.norm(a.astype(np.float64) - b) / max(np.linalg.norm(b), 1e-30))
+    e_p = rel(got["params"], tr.fp.flat.double().cpu().numpy())
+    e_b = rel(got["params"], before)
+    e_g = rel(got["grad"], tr.fp.grad.double().cpu().numpy())
+    print(f"dump vs in-process: params {e_p:.3g} (one step earlier {e_b:.3g}) grad {e_g:.3g}")
+    assert np.isfinite(got["grad"]).all() and np.abs(got["grad"]).max() > 0
+    assert e_g <= 1e-3
+    assert e_b > 0 and e_p <= 0.1 * e_b
+    assert got["stats"][12] == st["agent_steps"] and got["stats"][14] == st["T"]

@@ -98,3 +98,29 @@ def test_bench_world_mismatch_fails_fast():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--device", "cpu"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_and_full_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's parameters, gradient and statistics, identical
+    from run to run; --steps sets the number of timed steps; --full adds the per-phase timings
+    after them without moving what was dumped."""
+    import numpy as np
+    args = ["--gpus", "1", "--device", "cpu", "--agents", "8", "--envs", "2", "--warmup", "1", "--inner_loops", "3"]
+    outs = []
+    for d, extra in (("a", ["--steps", "2"]), ("b", ["--steps", "2", "--full"]), ("c", ["--steps", "1"])):
+        r = _bench(args + extra + ["--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == int(extra[1]) and out["ms_per_step"] > 0
+        assert ("phases_ms" in out) == ("--full" in extra)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["grad.npy", "params.npy", "stats.npy"]
+        outs.append({f: np.load(tmp_path / d / f) for f in files})
+    a, b, c = outs
+    assert a["params.npy"].dtype == np.float32 and a["params.npy"].shape == a["grad.npy"].shape == (51141,)
+    assert a["stats.npy"].dtype == np.float64 and np.isfinite(a["stats.npy"]).all()
+    assert np.abs(a["grad.npy"]).max() > 0
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
+    assert not np.array_equal(a["params.npy"], c["params.npy"])     # one timed step fewer
