@@ -193,6 +193,33 @@ struct CbfBwdArgs {
                                 // (scripts/stamps_cbf.py)
 };
 
+// Safety filter (refine.hip): gradient refinement of the actions on the discrete CBF condition,
+//   delta <- delta - lr d/d delta sum_e relu(-(h(s') - h + dt alpha h)),  s' = s + dt [v, a + delta],
+// one (refine_grad, refine_update) launch pair per iteration `it`, both on one stream.
+constexpr double FX_VIOL = 4294967296.0;   // 2^32: fixed-point scale of the violation sum
+struct RefineArgs {
+  const float4* S;  long s_env;            // node records of s_t: (b, node) -> S[(b*s_env + node) * REC]
+  int dim;                                 // 2 or 3
+  const int* idx;                          // (B,N,K) neighbour slots into the Nn graph nodes
+  const float* a;                          // (B,N,D) controller actions
+  float* delta;                            // (B,N,D) action correction (agents only), updated in place
+  const float* h;                          // (B,N,K) radius-masked h(s_t), fixed over the loop
+  int B, N, Nn, K;                         // N agents (the first N nodes), Nn graph nodes
+  const h16* wpack; int f_bwd;             // packed fragments: w1f at f_bwd, w1ft at f_bwd + 66
+  const h16* wrm;                          // row-major W2 | W3 images
+  const float* wvec;
+  float* dEv;                              // (B,N,K,D) velocity half of dL/d(s'_i - s'_j) per edge
+  const int* ptr; const int* edges;        // reverse CSR of the B graphs: (B, Nn+1) / (B, N*K)
+  // control words, zeroed before the loop: ctl[2*it] = edges with a non-zero hinge gradient in
+  // iteration it, ctl[2*it+1] = sum_e relu(-deriv_e) * FX_VIOL of iteration it (integer atomics)
+  unsigned long long* ctl;
+  int it;
+  float dt, dt_alpha, lr;
+  float obs_r, dist_thr, dist_eps;
+  float* hn_out;                           // trace (or null): (B,N,K) masked h(s') of this iteration
+  uint8_t* flag_out;                       // trace (or null): (B,N,K) 1 where the hinge gradient is on
+};
+
 // Deduplication of the h / h' evaluations (dedup.hip). h'(s_{t+1}) of slot (t,b,i,k) is the
 // same function value as h(s_{t+1}) of the slot (t+1,b,i,k') with the same neighbour, so only
 // the unmatched pairs ("extras") need their own evaluation.
@@ -412,6 +439,13 @@ int mb_k16_wg_per_cu_x3(int kernel);
 int mb_node_act_bytes();
 int mb_node_act_bytes_f16();
 int mb_node_act_bytes_x3();
+int mb_refine_grad(const mb::RefineArgs* a, int num_blocks, hipStream_t st);
+int mb_refine_grad_f16(const mb::RefineArgs* a, int num_blocks, hipStream_t st);
+int mb_refine_grad_x3(const mb::RefineArgs* a, int num_blocks, hipStream_t st);
+int mb_refine_prepare(int dim);
+int mb_refine_prepare_f16(int dim);
+int mb_refine_prepare_x3(int dim);
+int mb_refine_update(const mb::RefineArgs* a, hipStream_t st);
 int mb_rev_csr(const mb::CsrArgs* a, hipStream_t st);
 int mb_cbf_match(const mb::CbfMatchArgs* a, hipStream_t st);
 int mb_cbf_dh(const mb::CbfDhArgs* a, int num_blocks, hipStream_t st);

@@ -19,8 +19,8 @@ ROOT = os.path.dirname(HERE)
 PKG = os.path.join(ROOT, "macbf_gnn_amd")
 BUILD = os.path.join(ROOT, "build", "csrc")
 ARCH = os.environ.get("MACBF_ARCH", "gfx950")
-KERNELS = ["scan", "scenario", "ctrl", "cbf", "dedup", "graph", "optim"]
-HALF_KERNELS = {"ctrl", "cbf"}       # compiled per MFMA operand precision (csrc/prec.h)
+KERNELS = ["scan", "scenario", "ctrl", "cbf", "refine", "dedup", "graph", "optim"]
+HALF_KERNELS = {"ctrl", "cbf", "refine"}       # compiled per MFMA operand precision (csrc/prec.h)
 
 
 HOST_SRCS = ["host/scenario_host.cpp", "host/bindings_host.cpp"]   # CPU runtime (plain C++)

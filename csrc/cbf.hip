@@ -17,6 +17,7 @@
 #include "common.h"
 #include "args.h"
 #include "state.h"
+#include "cbf_edge.h"   // cbf_edge_frag, EdgeCtx, weight-image sizes (shared with refine.hip)
 
 // waves per 32x32x16 CBF-backward workgroup: x3 4 (one per SIMD: the split activations double
 // the register footprint), 1-pass 8 (two per SIMD)
@@ -24,47 +25,6 @@ constexpr int CBF_NW = MB_X3 ? 4 : 8;
 
 namespace mb {
 namespace MB_PREC {
-
-constexpr int CBF_FWD_FRAGS = 34;  // w1f 2 + w2 16 + w3 16
-constexpr int CBF_VEC = 260;       // b2 128 | b3 64 | w4 64 | b4 1 (+3 pad)
-
-
-
-// Layer-1 B fragment of one edge (K slots: see layout.cbf_w1_slot): fp32 features split into
-// h16 hi (lanes h = 0) and residual lo (lanes h = 1) parts.
-template <int D>
-DEV h16x8 cbf_edge_frag(const float (&rp)[D], const float (&rv)[D], float eye, float dfeat, bool ok, int h) {
-  h16x8 f;
-  const h16 z = (h16)0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f[j] = z;
-  if (!ok) return f;
-  h16 hi[2 * D + 1], lo[2 * D + 1];
-#pragma unroll
-  for (int q = 0; q < D; ++q) {
-    split_h16(rp[q], hi[q], lo[q]);
-    split_h16(rv[q], hi[D + q], lo[D + q]);
-  }
-  split_h16(dfeat, hi[2 * D], lo[2 * D]);
-  if constexpr (D == 2) {
-    if (h == 0) {
-      f[0] = hi[0]; f[1] = hi[1]; f[2] = hi[2]; f[3] = hi[3]; f[4] = (h16)eye; f[5] = hi[4]; f[6] = (h16)1.f;
-    } else {
-      f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3]; f[5] = lo[4];
-    }
-  } else {
-    if (h == 0) {
-#pragma unroll
-      for (int q = 0; q < 7; ++q) f[q] = hi[q];
-      f[7] = (h16)1.f;
-    } else {
-#pragma unroll
-      for (int q = 0; q < 7; ++q) f[q] = lo[q];
-      f[7] = (h16)eye;
-    }
-  }
-  return f;
-}
 
 struct CbfActs { f32x16 H1[2], H2[4], H3[2]; };
 
@@ -108,15 +68,6 @@ DEV float cbf_mlp(const h16x8& F, const h16* wl, const float* vl, int lane, CbfA
   s += shfl_xor32(s);
   return s + b4;
 }
-
-template <int D>
-struct EdgeCtx {
-  bool ok;
-  int b, t, i, j;
-  float rp[D], rv[D];     // s_i - s_j: positions, velocities
-  float eye, d, dfeat;
-  bool mask;
-};
 
 // 32-bit index math throughout (host asserts passes*E < 2^31): 64-bit divisions/multiplies
 // here cost dozens of VGPRs and instructions per edge. Strides are in node records.
@@ -283,10 +234,7 @@ namespace MB_PREC {
 // 16-lane group): 68 = 34 dwords and 148 = 74 dwords keep 32-row weight reads, 4-row transposed
 // reads and 16-row tile stores conflict-free or 2-way at most (72 / 136 were 2-4 way).
 constexpr int SA128 = 148, SA64 = 68, SA32 = 40;
-constexpr int WS2 = 68, WS3 = 148;                  // row-major W2 [128][WS2], W3 [64][WS3] images
-constexpr int RM_W2 = 128 * WS2, RM_W3 = 64 * WS3;  // row-major image sizes (elements)
-constexpr int RM_LO = RM_W2 + RM_W3;                // lo plane offset of the images (x3)
-constexpr int RMP = (X3 ? 2 : 1) * RM_LO;           // elements of the W2|W3 (+ lo) images
+// (WS2 / WS3 and the RM_* sizes of the row-major W2 | W3 images: cbf_edge.h)
 // per-WG partial slab layout (floats)
 constexpr int P_W3 = 0, P_B3 = 8192, P_W2 = 8256, P_B2 = 16448, P_W1 = 16576, P_W4 = 18624, P_B4 = 18688;
 constexpr int P_LOSS = 18692;                 // 10 loss partial sums (fused mode)

@@ -1,6 +1,6 @@
 // MFMA operand precision of the network kernels.
 //
-// ctrl.hip and cbf.hip are compiled three times (csrc/build.py):
+// ctrl.hip, cbf.hip and refine.hip are compiled three times (csrc/build.py):
 //   bf16 (default)  one v_mfma_f32_32x32x16_bf16 per product, fp32 accumulation
 //   fp16 (-DMB_FP16=1) the same with v_mfma_f32_32x32x16_f16 ("fp16 mixed precision")
 //   x3   (-DMB_X3=1)   fp32-accurate: every operand is split x = hi + lo into two bf16 planes and

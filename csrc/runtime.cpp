@@ -529,9 +529,49 @@ class BpttDriver {
   float dt_, sqrt3_;
 };
 
+// Safety-filter loop (csrc/refine.hip): `loops` x (refine_grad, refine_update) on the caller's
+// stream. The pointers and sizes are validated once; the control words (2 per iteration) are
+// cleared here; nothing is allocated or built; no host synchronisation -- the early-out lives in the
+// kernels. hn_out / flag_out (optional) receive the first iteration's h(s') and hinge flags.
+int refine_loop(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, int B, int N, int Nn, int K, u64 wpack,
+                int f_bwd, u64 wrm, u64 wvec, u64 dEv, u64 ptr, u64 edges, u64 ctl, int loops, float dt, float dt_alpha,
+                float lr, float obs_r, float dist_thr, float dist_eps, u64 hn_out, u64 flag_out, int num_blocks,
+                int prec, u64 stream) {
+  if (dim != 2 && dim != 3) return -1;
+  if (B < 1 || N < 1 || Nn < N || K < 1 || K > 16 || loops < 0 || num_blocks < 1 || f_bwd < 0 || s_env < Nn) return -1;
+  if (prec < 0 || prec > 2) return -1;
+  if (!S || !idx || !a || !delta || !h || !wpack || !wrm || !wvec || !dEv || !ptr || !edges || !ctl) return -2;
+  if (loops == 0) return 0;
+  hipStream_t st = ST(stream);
+  mb::RefineArgs r{};
+  r.S = P<const float4>(S); r.s_env = s_env; r.dim = dim; r.idx = P<const int>(idx);
+  r.a = P<const float>(a); r.delta = P<float>(delta); r.h = P<const float>(h);
+  r.B = B; r.N = N; r.Nn = Nn; r.K = K;
+  r.wpack = P<const h16>(wpack); r.f_bwd = f_bwd; r.wrm = P<const h16>(wrm); r.wvec = P<const float>(wvec);
+  r.dEv = P<float>(dEv); r.ptr = P<const int>(ptr); r.edges = P<const int>(edges);
+  r.ctl = P<unsigned long long>(ctl);
+  r.dt = dt; r.dt_alpha = dt_alpha; r.lr = lr; r.obs_r = obs_r; r.dist_thr = dist_thr; r.dist_eps = dist_eps;
+  const hipError_t e = hipMemsetAsync(r.ctl, 0, (size_t)loops * 2 * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return (int)e;
+  const auto grad = prec == 2 ? mb_refine_grad_x3 : prec == 1 ? mb_refine_grad_f16 : mb_refine_grad;
+  const int pr = (prec == 2 ? mb_refine_prepare_x3 : prec == 1 ? mb_refine_prepare_f16 : mb_refine_prepare)(dim);
+  if (pr) return pr;
+  for (int it = 0; it < loops; ++it) {
+    r.it = it;
+    r.hn_out = it == 0 ? P<float>(hn_out) : nullptr;
+    r.flag_out = it == 0 ? P<uint8_t>(flag_out) : nullptr;
+    int rc = grad(&r, num_blocks, st);
+    if (rc) return rc;
+    rc = mb_refine_update(&r, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 }  // namespace
 
 void register_runtime(py::module& m) {
+  m.def("refine_loop", &refine_loop);
   py::class_<BpttDriver>(m, "BpttDriver")
       .def(py::init<py::dict>())
       .def("run", &BpttDriver::run, py::arg("T"), py::arg("act_coef"), py::arg("stream"), py::arg("use_acts") = false);

@@ -2,12 +2,16 @@
 
     python evaluate.py --num_agents 32 [--model_path ckpt.pt] [--num_envs 4] [--episodes 10]
                        [--max_steps 50] [--no_refine] [--refine_space actions|gains] [--diagnose]
-                       [--device auto|cpu|hip] [--gpu 0]
+                       [--dim 2|3] [--num_obstacles M] [--dtype fp32|bf16|fp16]
+                       [--refine_impl autograd|native] [--device auto|cpu|hip] [--gpu 0]
 
 Prints one JSON line: safety rate, reaching rate, mean final goal distance, refinement
 iterations. Without --model_path the networks are random-initialised (plumbing check).
 --refine_space gains refines only the PD gains of the controller law (what the trained policy
 class can express); --diagnose adds the share of unsafe pairs that are top-K neighbours.
+--dim / --num_obstacles select the scene family (a checkpoint's dimension is read from its CBF
+input layer and must agree with --dim); --dtype is the MFMA operand precision on a HIP device;
+--refine_impl native runs the refinement as the device-resident safety filter (HIP only).
 """
 from __future__ import annotations
 
@@ -31,6 +35,10 @@ def main(argv=None):
     ap.add_argument("--diagnose", action="store_true")
     ap.add_argument("--device", type=str, default="auto")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dim", type=int, choices=[2, 3], default=2)
+    ap.add_argument("--num_obstacles", type=int, default=0)
+    ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32")
+    ap.add_argument("--refine_impl", choices=["autograd", "native"], default="autograd")
     args = ap.parse_args(argv)
     if args.gpu is not None:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)
@@ -43,11 +51,20 @@ def main(argv=None):
 
     dev = resolve_device(args.device)
     torch.manual_seed(args.seed)
-    ctrl, cbf = Controller(4).to(dev), CBF(4).to(dev)
+    if args.refine_impl == "native" and dev.type != "cuda":
+        ap.error("--refine_impl native is the HIP safety filter and needs a HIP device; "
+                 "use --refine_impl autograd with --device cpu")
+    if args.model_path:
+        ck_dim = ckpt.model_dim(args.model_path)
+        if ck_dim is not None and ck_dim != args.dim:
+            ap.error(f"checkpoint {args.model_path} holds {ck_dim}-D networks (CBF input width {2 * ck_dim + 2}) "
+                     f"but --dim is {args.dim}; pass --dim {ck_dim}")
+    ctrl, cbf = Controller(2 * args.dim).to(dev), CBF(2 * args.dim).to(dev)
     if args.model_path:
         ckpt.load_models(args.model_path, ctrl, cbf)
     cfg = EvalConfig(num_agents=args.num_agents, num_envs=args.num_envs, seed=args.seed, refine=not args.no_refine,
-                     refine_space=args.refine_space, diagnose=args.diagnose)
+                     refine_space=args.refine_space, diagnose=args.diagnose, dim=args.dim,
+                     num_obstacles=args.num_obstacles, dtype=args.dtype, refine_impl=args.refine_impl)
     if args.episodes is not None:
         cfg.episodes = args.episodes
     if args.max_steps is not None:
@@ -58,7 +75,8 @@ def main(argv=None):
         cfg.refine_lr = args.refine_lr
     out = evaluate(ctrl, cbf, cfg, device=dev)
     out.update({"num_agents": args.num_agents, "num_envs": args.num_envs, "episodes": cfg.episodes,
-                "refine": cfg.refine, "device": str(dev)})
+                "refine": cfg.refine, "device": str(dev), "dim": cfg.dim, "num_obstacles": cfg.num_obstacles,
+                "refine_impl": cfg.refine_impl, "dtype": cfg.dtype})
     print(json.dumps(out), flush=True)
     return out
 

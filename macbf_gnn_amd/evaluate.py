@@ -2,6 +2,10 @@
 ``EVALUATE_STEPS``, ``REFINE_LOOPS``, ``REFINE_LEARNING_RATE`` at ``config.py:17,19-20`` but never
 uses them).
 
+Scenes are D-dimensional (D = 2 or 3) double integrators, optionally with static obstacle points
+that join the graph as non-controlled nodes (``oracle.with_obstacles``): kNN, the CBF and the
+safety check see agents + obstacle points, actions exist for the agents only.
+
 Per rollout step:
     idx     = kNN(s_t)                                   (K1, native on the HIP device)
     a       = pi(s_t, g)                                 (controller)
@@ -14,7 +18,9 @@ Metrics: safety rate (all-pairs TTC check with DIST_MIN_CHECK / TIME_TO_COLLISIO
 end), mean final goal distance and refinement statistics.
 
 On a HIP device the CBF and controller run through the native autograd Functions
-(``ops/cbf.py``, ``ops/ctrl.py``); on CPU through the fp32 oracle.
+(``ops/cbf.py``, ``ops/ctrl.py``); on CPU through the fp32 oracle. ``refine_impl="native"`` (HIP
+only, opt-in) runs the action refinement as the device-resident safety filter of
+``ops/refine.py`` (``csrc/refine.hip``) instead of the autograd loop.
 """
 from __future__ import annotations
 
@@ -43,40 +49,62 @@ class EvalConfig:
     refine_space: str = "actions"   # "actions" (upstream MACBF) or "gains": refine only the PD gains
                                     # of the reference controller law (controller.py:53-61) -- what
                                     # the trained policy class itself can express
+    dim: int = 2                # spatial dimension of the scenes (2 or 3)
+    num_obstacles: int = 0      # static point-set obstacles per scene
+    obstacle_points: int = 12   # points per obstacle (HIP sampler; the host sampler uses its default)
+    dtype: str = "fp32"         # MFMA operand precision on HIP: evaluate() sets the networks' mfma_dtype
+                                # (fp32 | bf16 | fp16); no effect on CPU (fp32 oracle)
+    refine_impl: str = "autograd"   # "autograd" or "native" (HIP only): the device-resident filter
 
 
-def _knn(s, k):
+MFMA_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+
+
+def _knn(s, k, obstacles=None):
     if s.is_cuda:
         from .ops import graph
-        return graph.knn(s, k).long()
-    return oracle.knn_idx(s, k)
+        return graph.knn(s, k, obstacles).long()
+    if obstacles is None:
+        return oracle.knn_idx(s, k)
+    return oracle.knn_idx(s, k, oracle.with_obstacles(s, obstacles))
 
 
-def _safe_count(s):
+def _safe_count(s, obstacles=None):
     if s.is_cuda:
         from .ops import graph
-        return graph.safe_agent_count(s)
-    return oracle.safe_agent_count(s).float()
+        return graph.safe_agent_count(s, obstacles)
+    if obstacles is None:
+        return oracle.safe_agent_count(s).float()
+    return oracle.safe_agent_count(s, oracle.with_obstacles(s, obstacles)).float()
+
+
+def _euler(s, a):
+    """s_{t+1} = s_t + dt [v, a] of the D-dimensional double integrator."""
+    D = s.shape[-1] // 2
+    return s + torch.cat([s[..., D:], a], -1) * C.TIME_STEP
 
 
 def refine_actions(cbf, s, a, idx, loops: int = C.REFINE_LOOPS, lr: float = C.REFINE_LEARNING_RATE,
-                   check_every: int = 10):
+                   check_every: int = 10, obstacles=None):
     """Gradient refinement of the actions on the discrete CBF condition. Returns
     (refined actions, iterations used, remaining violation sum).
 
     The violation is a hinge: once it is exactly zero its gradient is exactly zero, so further
     iterations leave the actions unchanged. The loop therefore only looks at the violation on
     the host every ``check_every`` iterations (one sync instead of one per iteration); the
-    iteration count (iterations that still had a violation) is kept on the device."""
+    iteration count (iterations that still had a violation) is kept on the device.
+
+    ``obstacles`` (B, M, D): static points among the neighbour slots of ``idx``; they have no action
+    and do not move, so ``delta`` stays (B, N, D)."""
     with torch.no_grad():
-        h = cbf(s, idx=idx)
+        h = cbf(s, idx=idx, obstacles=obstacles)
     delta = torch.zeros_like(a, requires_grad=True)
     viol = torch.zeros((), device=s.device)
     used = torch.zeros((), dtype=torch.int64, device=s.device)
     for it in range(1, loops + 1):
         ar = a + delta
-        s_next = s + torch.cat([s[..., 2:], ar], -1) * C.TIME_STEP
-        hn = cbf(s_next, idx=idx)
+        s_next = _euler(s, ar)
+        hn = cbf(s_next, idx=idx, obstacles=obstacles)
         deriv = hn - h + C.TIME_STEP * C.ALPHA_CBF * h
         viol = torch.relu(-deriv).sum()
         pending = viol.detach() > 0
@@ -98,12 +126,12 @@ def _pd_action(s, g, y):
 
 
 def refine_gains(cbf, s, g, k0, idx, loops: int = C.REFINE_LOOPS, lr: float = C.REFINE_LEARNING_RATE,
-                 check_every: int = 10):
+                 check_every: int = 10, obstacles=None):
     """refine_actions restricted to the controller's action space: gradient steps on the gain
     pre-activations y (k = 2 sigmoid(y) + 0.2, started at the network's gains k0) instead of free
     actions."""
     with torch.no_grad():
-        h = cbf(s, idx=idx)
+        h = cbf(s, idx=idx, obstacles=obstacles)
         u = ((k0 - 0.2) / 2.0).clamp(1e-6, 1 - 1e-6)
         y = torch.log(u / (1 - u))
     y = y.clone().requires_grad_(True)
@@ -111,8 +139,8 @@ def refine_gains(cbf, s, g, k0, idx, loops: int = C.REFINE_LOOPS, lr: float = C.
     used = torch.zeros((), dtype=torch.int64, device=s.device)
     for it in range(1, loops + 1):
         a = _pd_action(s, g, y)
-        s_next = s + torch.cat([s[..., 2:], a], -1) * C.TIME_STEP
-        hn = cbf(s_next, idx=idx)
+        s_next = _euler(s, a)
+        hn = cbf(s_next, idx=idx, obstacles=obstacles)
         viol = torch.relu(-(hn - h + C.TIME_STEP * C.ALPHA_CBF * h)).sum()
         pending = viol.detach() > 0
         used += pending.long()
@@ -125,10 +153,11 @@ def refine_gains(cbf, s, g, k0, idx, loops: int = C.REFINE_LOOPS, lr: float = C.
         return _pd_action(s, g, y), int(used), float(viol.detach())
 
 
-def _unsafe_diag(s_next, idx):
+def _unsafe_diag(s_next, idx, obstacles=None):
     """(unsafe agents, unsafe agents whose every flagged pair is one of their top-K neighbours at
     the step's graph) -- do the controller / CBF see the pairs that the safety check flags?"""
-    dang = oracle.ttc_mask_all_pairs(s_next)                  # (B, N, N) check mask
+    nodes = None if obstacles is None else oracle.with_obstacles(s_next, obstacles)
+    dang = oracle.ttc_mask_all_pairs(s_next, nodes)           # (B, N, Nn) check mask
     unsafe = dang.any(-1)
     in_k = torch.zeros_like(dang)
     in_k.scatter_(-1, idx.long(), True)
@@ -136,43 +165,62 @@ def _unsafe_diag(s_next, idx):
     return unsafe.sum(), seen.sum()
 
 
-def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig) -> Dict[str, float]:
+def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dict[str, float]:
+    """One batch of episodes from ``s0`` (B, N, 2D) towards ``g`` (B, N, D); ``obstacles`` (B, M, D)
+    are static graph nodes seen by kNN, the controller, the CBF and the safety check."""
+    if cfg.refine_impl not in ("autograd", "native"):
+        raise ValueError(f"unknown refine_impl {cfg.refine_impl!r} (autograd or native)")
+    native_filter = cfg.refine and cfg.refine_impl == "native" and cfg.refine_space != "gains"
+    if cfg.refine_impl == "native" and not s0.is_cuda:
+        raise ValueError("refine_impl='native' is the HIP safety filter (csrc/refine.hip): it needs a HIP device; "
+                         "use refine_impl='autograd' on CPU")
     s = s0
     B, N, _ = s.shape
+    D = s.shape[-1] // 2
+    obs = obstacles
     k = min(cfg.top_k, N)
     safe_sum = 0.0
     steps = 0
     refine_iters = 0
+    iters_dev = torch.zeros((), dtype=torch.int64, device=s.device)   # native filter: read once per episode
     unsafe_n = torch.zeros((), device=s.device)
     seen_n = torch.zeros((), device=s.device)
     active = torch.ones(B, dtype=torch.bool, device=s.device)
     for t in range(cfg.max_steps):
-        idx = _knn(s, k)
+        idx = _knn(s, k, obs)
         with torch.no_grad():
-            a = controller(s, g, idx=idx)
+            a = controller(s, g, idx=idx, obstacles=obs)
         if cfg.refine and cfg.refine_space == "gains":
             with torch.no_grad():
-                _, aux = oracle.controller_forward(controller.params_dict(), s, g, idx, return_aux=True)
-            a, it, _ = refine_gains(cbf, s, g, aux["gains"], idx, cfg.refine_loops, cfg.refine_lr)
+                nodes = None if obs is None else oracle.with_obstacles(s, obs)
+                _, aux = oracle.controller_forward(controller.params_dict(), s, g, idx, return_aux=True, nodes=nodes)
+            a, it, _ = refine_gains(cbf, s, g, aux["gains"], idx, cfg.refine_loops, cfg.refine_lr, obstacles=obs)
             refine_iters += it
+        elif native_filter:
+            from .ops import refine as refine_ops
+            a, used, _ = refine_ops.safety_filter(cbf, s, a, idx, obstacles=obs, loops=cfg.refine_loops,
+                                                  lr=cfg.refine_lr)
+            iters_dev += used
         elif cfg.refine:
-            a, it, _ = refine_actions(cbf, s, a, idx, cfg.refine_loops, cfg.refine_lr)
+            a, it, _ = refine_actions(cbf, s, a, idx, cfg.refine_loops, cfg.refine_lr, obstacles=obs)
             refine_iters += it
         with torch.no_grad():
-            s = s + torch.cat([s[..., 2:], a], -1) * C.TIME_STEP
-            safe = _safe_count(s)
+            s = _euler(s, a)
+            safe = _safe_count(s, obs)
             safe_sum += float((safe * active.float()).sum())
             if cfg.diagnose:
-                u, sn = _unsafe_diag(s[active], idx[active])
+                u, sn = _unsafe_diag(s[active], idx[active], None if obs is None else obs[active])
                 unsafe_n += u
                 seen_n += sn
             steps += int(active.sum()) * N
-            dist = torch.linalg.vector_norm(s[..., :2] - g, dim=-1).mean(-1)
+            dist = torch.linalg.vector_norm(s[..., :D] - g, dim=-1).mean(-1)
             active = active & (dist >= C.DIST_MIN_CHECK)
         if cfg.early_stop and not bool(active.any()):
             break
+    if native_filter:
+        refine_iters += int(iters_dev)
     with torch.no_grad():
-        d = torch.linalg.vector_norm(s[..., :2] - g, dim=-1)
+        d = torch.linalg.vector_norm(s[..., :D] - g, dim=-1)
         reach = float((d < C.DIST_MIN_CHECK).float().mean())
         mean_dist = float(d.mean())
     out = {"safety_rate": safe_sum / max(steps, 1), "reaching_rate": reach, "mean_goal_dist": mean_dist,
@@ -183,21 +231,42 @@ def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig) -> Dict[str, float]:
     return out
 
 
+def sample_scenarios(cfg: EvalConfig, episode: int, device):
+    """(s0, g, obstacles or None) of one evaluation episode. HIP: the on-device sampler. CPU: the
+    2-D obstacle-free case keeps ``env.generate_batch`` and its seed formula (published numbers do
+    not move); every other scene comes from ``env.generate_scenarios`` with the same seed."""
+    from . import env as E
+    if device.type == "cuda":
+        from .ops import scenario
+        return scenario.generate(cfg.num_envs, cfg.num_agents, seed=cfg.seed + 7919, iteration=episode, rank=0,
+                                 device=device, dim=cfg.dim, num_obstacles=cfg.num_obstacles,
+                                 obstacle_points=cfg.obstacle_points)
+    if cfg.dim == 2 and cfg.num_obstacles == 0:
+        s0, g = E.generate_batch(cfg.num_envs, cfg.num_agents, C.DIST_MIN_THRES, seed=cfg.seed * 7919 + episode)
+        return s0, g, None
+    return E.generate_scenarios(cfg.num_envs, cfg.num_agents, cfg.dim, cfg.num_obstacles,
+                                seed=cfg.seed * 7919 + episode)
+
+
 def evaluate(controller, cbf, cfg: EvalConfig, device: Optional[torch.device] = None) -> Dict[str, float]:
     """Run ``cfg.episodes`` fresh scenarios; returns metrics averaged over episodes."""
-    from . import env as E
     device = device or next(controller.parameters()).device
+    if cfg.dim not in (2, 3):
+        raise ValueError(f"dim must be 2 or 3, got {cfg.dim}")
+    for name, net in (("controller", controller), ("cbf", cbf)):
+        if getattr(net, "in_dim", 2 * cfg.dim) != 2 * cfg.dim:
+            raise ValueError(f"{name} was built for {net.in_dim // 2}-D states, the evaluation runs dim={cfg.dim}")
+    if cfg.dtype not in MFMA_DTYPES:
+        raise ValueError(f"dtype must be one of {sorted(MFMA_DTYPES)}, got {cfg.dtype!r}")
+    if device.type == "cuda":
+        controller.mfma_dtype = cbf.mfma_dtype = MFMA_DTYPES[cfg.dtype]
     controller.eval()
     cbf.eval()
     agg: Dict[str, float] = {}
     for ep in range(cfg.episodes):
-        if device.type == "cuda":
-            from .ops import scenario
-            s0, g, _ = scenario.generate(cfg.num_envs, cfg.num_agents, seed=cfg.seed + 7919, iteration=ep, rank=0,
-                                      device=device)
-        else:
-            s0, g = E.generate_batch(cfg.num_envs, cfg.num_agents, C.DIST_MIN_THRES, seed=cfg.seed * 7919 + ep)
-        r = rollout_eval(controller, cbf, s0.to(device), g.to(device), cfg)
+        s0, g, obs = sample_scenarios(cfg, ep, device)
+        r = rollout_eval(controller, cbf, s0.to(device), g.to(device), cfg,
+                         obstacles=None if obs is None else obs.to(device))
         for kk, v in r.items():
             agg[kk] = agg.get(kk, 0.0) + float(v)
     return {kk: v / cfg.episodes for kk, v in agg.items()}

@@ -817,6 +817,89 @@ def node_combine(dS_t, ego, dEc, rptr_t, redges_t, Gn, Gout, *, K, dt=C.TIME_STE
                            ptr(Gout), Gout.stride(0) // W, B, N, K, float(dt), D, stream_handle()), "node_combine")
 
 
+# ----------------------------------------------------------------------------- safety filter
+FX_VIOL = 2.0 ** 32           # csrc/args.h: fixed-point scale of the violation sums
+
+
+def refine_grid(E: int, device, prec_code: int) -> int:
+    """Workgroups of refine_grad over E edges: one per CU (csrc/refine.hip REFINE_NW waves each,
+    a 32-edge tile per wave per trip)."""
+    waves = 4 if prec_code == 2 else 8
+    tiles = (E + 31) // 32
+    return max(1, min((tiles + waves - 1) // waves, num_cu(device)))
+
+
+def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl, *, loops, lr,
+           prec=None, hn_out=None, flag_out=None, num_blocks=None):
+    """The safety-filter loop (csrc/refine.hip + the driver in csrc/runtime.cpp): ``loops`` gradient
+    steps of ``delta`` (B, N, D), in place, on sum_e relu(-(h(s') - h + dt alpha h)) with
+    s' = s + dt [v, a + delta].
+
+    S (B, Nn, 4|8) node records of s_t (agents first); idx (B, N, K) int32 into the Nn nodes;
+    a / delta (B, N, D) fp32 contiguous; h (B, N, K) the radius-masked h(s_t); wpack / wrm / wvec the
+    packed CBF weights (``module_pack``); dEv (B, N, K, D) workspace; rptr (B, Nn+1) / redges
+    (B, N*K) the reverse CSR of idx (``rev_csr``); ctl int64, >= 2*loops words, cleared by the
+    driver: ctl[2 it] = edges with a non-zero hinge gradient in iteration it, ctl[2 it + 1] = the
+    violation sum of iteration it times FX_VIOL. hn_out (B, N, K) fp32 / flag_out (B, N, K) uint8
+    (optional): h(s') and the hinge flags of the first iteration. No host synchronisation.
+    fp32 (x3) and bf16 builds; fp16 is not supported (the -1 upstream gradient has no loss scaling)."""
+    if S is None or S.dim() != 3:
+        raise NativeError("S must be (B, Nn, 4|8) node records")
+    B, Nn, W = S.shape
+    D = dim_of(S)
+    check(S, torch.float32, (B, Nn, W), "S")
+    if idx is None or idx.dim() != 3 or idx.shape[0] != B:
+        raise NativeError(f"idx must be int32 (B={B}, N, K)")
+    _, N, K = idx.shape
+    check(idx, torch.int32, (B, N, K), "idx")
+    if K < 1 or K > C.MAX_TOP_K:
+        raise NativeError(f"K = {K} outside 1..{C.MAX_TOP_K}")
+    if N < 1 or N > Nn:
+        raise NativeError(f"idx has N = {N} agents but S holds {Nn} nodes")
+    for t, name in ((a, "a"), (delta, "delta")):
+        if t is None:
+            raise NativeError(f"{name} is required")
+        check(t, torch.float32, (B, N, D), name)
+    if h is None or dEv is None or rptr is None or redges is None or ctl is None:
+        raise NativeError("h, dEv, rptr, redges and ctl are required")
+    check(h, torch.float32, (B, N, K), "h")
+    check(dEv, torch.float32, (B, N, K, D), "dEv")
+    check(rptr, torch.int32, (B, Nn + 1), "rptr")
+    check(redges, torch.int32, (B, N * K), "redges")
+    loops = int(loops)
+    if loops < 0:
+        raise NativeError("loops must be >= 0")
+    check(ctl, torch.int64, None, "ctl")
+    if ctl.dim() != 1 or ctl.numel() < 2 * loops:
+        raise NativeError(f"ctl must be int64 with at least 2*loops = {2 * loops} words, got {tuple(ctl.shape)}")
+    code = _half(wpack, "wpack", prec)
+    if code == 1:
+        raise NativeError("safety filter: fp16 is not supported (the -1 upstream gradient has no loss scaling); "
+                          "use fp32 or bf16")
+    check(wpack, wpack.dtype, None, "wpack")
+    check(wvec, torch.float32, None, "wvec")
+    if wvec is None or wvec.numel() < 260:
+        raise NativeError("CBF side vector too small")
+    if f_bwd < 0 or wpack.numel() < (f_bwd + 70) * 512 * _planes(code):
+        raise NativeError("packed CBF weights too small")
+    check(wrm, wpack.dtype, (_planes(code) * (128 * 68 + 64 * 148),), "wrm")
+    check(hn_out, torch.float32, (B, N, K), "hn_out")
+    check(flag_out, torch.uint8, (B, N, K), "flag_out")
+    E = B * N * K
+    if E >= 2 ** 31 - 2 ** 21:
+        raise NativeError("too many edges for 32-bit indexing")
+    nb = int(num_blocks) if num_blocks else refine_grid(E, S.device, code)
+    if nb < 1 or nb > 4096:
+        raise NativeError("num_blocks outside 1..4096")
+    rc = lib().refine_loop(ptr(S), Nn, D, ptr(idx), ptr(a), ptr(delta), ptr(h), B, N, Nn, K, ptr(wpack), int(f_bwd),
+                           ptr(wrm), ptr(wvec), ptr(dEv), ptr(rptr), ptr(redges), ptr(ctl), loops,
+                           float(C.TIME_STEP), float(C.TIME_STEP * C.ALPHA_CBF), float(lr), float(C.OBS_RADIUS),
+                           float(C.DIST_MIN_THRES), float(C.CBF_DIST_EPS_COORD * D), ptr(hn_out), ptr(flag_out),
+                           nb, code, stream_handle())
+    _ok(rc, "refine")
+    return nb
+
+
 CTRL_EDGE_WAVES = 4          # csrc/ctrl.hip EB_WAVES
 
 

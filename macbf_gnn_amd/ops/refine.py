@@ -1,0 +1,83 @@
+"""Device-resident CBF safety filter (``csrc/refine.hip``): the action refinement of
+``evaluate.refine_actions`` without autograd and without a host synchronisation.
+
+    h      = h(s_t) on the kNN slots (one ``cbf_fwd`` launch), fixed over the loop
+    s'     = s + dt [v, a + delta]        (agents; obstacle nodes are static)
+    loss   = sum_e relu(-(h(s') - h + dt alpha h))
+    delta <- delta - lr dloss/ddelta      for at most ``loops`` iterations
+
+``used`` counts the iterations that still had an edge with a non-zero hinge gradient (violated,
+and inside the radius at s' -- outside it h(s') is 0 whatever the action); once an iteration has
+none, the remaining launches return at once and the actions stay as they are. ``viol`` is the
+hinge sum at the last evaluated iterate, as ``refine_actions`` reports it.
+"""
+from __future__ import annotations
+
+import torch
+
+from .. import config as C
+from . import graph, native
+from .packing import module_pack
+
+
+def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_LOOPS,
+                  lr: float = C.REFINE_LEARNING_RATE, return_trace: bool = False):
+    """s (B, N, 2D), a (B, N, D), idx (B, N, K) on the HIP device, obstacles (B, M, D) or None ->
+    (a_refined (B, N, D), used, viol); ``used`` (int64) and ``viol`` (float64) are 0-d device
+    tensors -- the caller decides when to read them. ``return_trace=True`` appends a dict with the
+    per-iteration active-edge counts ``counts`` (loops,), and ``hn`` (B, N, K) / ``active`` (B, N, K)
+    bool of the first iteration (tests)."""
+    if not s.is_cuda:
+        raise native.NativeError("the safety filter runs on the HIP device")
+    if s.dim() != 3 or a.dim() != 3 or idx.dim() != 3:
+        raise native.NativeError("s (B, N, 2D), a (B, N, D) and idx (B, N, K) are required")
+    B, N, SD = s.shape
+    D = SD // 2
+    K = idx.shape[-1]
+    loops = int(loops)
+    dev = s.device
+    mp = module_pack("cbf", cbf_module, dev)
+    if mp.prec == "fp16":
+        raise native.NativeError("safety filter: fp16 is not supported (the -1 upstream gradient has no loss "
+                                 "scaling); use fp32 or bf16")
+    if mp.dim != D:
+        raise native.NativeError(f"the CBF was built for {mp.dim}-D states, s is {D}-D")
+    obs = None
+    if obstacles is not None:
+        obs = obstacles if obstacles.dim() == 3 else obstacles.unsqueeze(0)
+        obs = obs.expand(B, *obs.shape[-2:]).float()
+    with torch.no_grad():
+        w, v, rm = mp.pack(list(cbf_module.parameters()))
+        S = graph.node_records(s, obs)                           # (B, Nn, W)
+        Nn = S.shape[1]
+        idx32 = idx.to(torch.int32).contiguous()
+        a32 = a.detach().float().contiguous()
+        delta = torch.zeros_like(a32)
+        h = torch.empty(1, B, N, K, dtype=torch.float32, device=dev)
+        ctl = torch.zeros(max(2 * loops, 2), dtype=torch.int64, device=dev)
+        hn = flags = None
+        if return_trace:
+            hn = torch.zeros(B, N, K, dtype=torch.float32, device=dev)
+            flags = torch.zeros(B, N, K, dtype=torch.uint8, device=dev)
+        if loops > 0:
+            native.cbf_fwd(S.view(1, *S.shape), idx32.view(1, B, N, K), w, mp.off["w1f"], v, two=False, h_out=h,
+                           prec=mp.prec)
+            rptr = torch.empty(B, Nn + 1, dtype=torch.int32, device=dev)
+            redges = torch.empty(B, N * K, dtype=torch.int32, device=dev)
+            native.rev_csr(idx32, rptr, redges, n_nodes=Nn)
+            dEv = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
+            native.refine(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, dEv, rptr, redges, ctl,
+                          loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags)
+        counts = ctl[0:2 * loops:2]
+        used = (counts > 0).sum()
+        if loops > 0:
+            # the violation of the last evaluated iterate: iteration `used` if it ran (it then counted
+            # no active edge), else the last one; selected on the device (no host read)
+            last = torch.clamp(used, max=loops - 1).view(1)
+            viol = ctl[1:2 * loops:2].index_select(0, last).view(()).double() / native.FX_VIOL
+        else:
+            viol = torch.zeros((), dtype=torch.float64, device=dev)
+        out = (a32 + delta).to(a.dtype)
+    if return_trace:
+        return out, used, viol, {"counts": counts.clone(), "hn": hn, "active": flags.bool() if flags is not None else None}
+    return out, used, viol

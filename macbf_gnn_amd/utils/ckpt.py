@@ -113,3 +113,18 @@ def load_models(path: str, controller, cbf, strict: bool = True):
         _load_module(controller, ck, strict)
     elif any(k.startswith("cbf_net") for k in keys) and cbf is not None:
         _load_module(cbf, ck, strict)
+
+
+def model_dim(path: str):
+    """Spatial dimension D of the networks in a checkpoint, from the input width of their first
+    layer (CBF ``cbf_net.0.weight``: 2D + 2 channels; controller edge net: 2D + 1), or None when
+    the file holds neither."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    for sd in (ck.get("cbf"), ck.get("controller"), ck):
+        if not isinstance(sd, dict):
+            continue
+        if "cbf_net.0.weight" in sd:
+            return (int(sd["cbf_net.0.weight"].shape[1]) - 2) // 2
+        if "controller_centr_net.0.weight" in sd:
+            return (int(sd["controller_centr_net.0.weight"].shape[1]) - 1) // 2
+    return None
