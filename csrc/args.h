@@ -218,6 +218,10 @@ struct RefineArgs {
   float obs_r, dist_thr, dist_eps;
   float* hn_out;                           // trace (or null): (B,N,K) masked h(s') of this iteration
   uint8_t* flag_out;                       // trace (or null): (B,N,K) 1 where the hinge gradient is on
+  // per-env mask (or null: every env), (B,) device memory, read by the kernels only. An env with 0
+  // here is left out: its edges are "not in the tile", its delta stays zero, and the control
+  // words count the other envs alone.
+  const uint8_t* env_active;
 };
 
 // Deduplication of the h / h' evaluations (dedup.hip). h'(s_{t+1}) of slot (t,b,i,k) is the

@@ -17,6 +17,11 @@
 // fixed point) are integer atomics: order independent, so the loop is reproducible bit for bit.
 // Early-out on the device: a zero hinge has a zero gradient, so once an iteration counted no
 // active edge every later launch returns at once and delta stays as it is.
+// Per-env mask (env_active, optional): the edges of an env with 0 are "not in the tile" (no dEv,
+// trace, count or violation term), a tile without a live edge skips the MFMA chain on a ballot
+// (wave-uniform: tiles straddle envs whenever N*K is no multiple of 32), and the update leaves the
+// env's delta at zero. The control words then count the other envs alone, so a batch stops when
+// its live envs are clean, exactly as the filter run on those envs alone would.
 #pragma clang fp contract(off)
 #include "common.h"
 #include "args.h"
@@ -44,14 +49,16 @@ struct RefIn {
 };
 
 // Edge e = (b*N + i)*K + k of a tile: every load is unconditional on a clamped index (idx holds
-// node ids up to Nn - 1, a / delta have N rows: an obstacle neighbour reads row N - 1 and is zeroed)
+// node ids up to Nn - 1, a / delta have N rows: an obstacle neighbour reads row N - 1 and is zeroed).
+// An edge of a masked-out env loads like any other and is then marked as not in the tile.
 template <int D>
 DEV void refine_load(const RefineArgs& a, unsigned tile, int r, unsigned E, RefIn<D>& x) {
   const unsigned e = tile * 32u + (unsigned)r;
-  x.in = e < E;
-  const unsigned ec = x.in ? e : 0u;
+  const bool inside = e < E;
+  const unsigned ec = inside ? e : 0u;
   const unsigned ik = ec / (unsigned)a.K;
   const unsigned b = ik / (unsigned)a.N;
+  x.in = inside && (a.env_active ? a.env_active[b] != 0 : true);
   const unsigned i = ik - b * (unsigned)a.N;
   const int jr = a.idx[ec];
   const unsigned j = (unsigned)min(max(jr, 0), a.Nn - 1);
@@ -106,6 +113,9 @@ __global__ __launch_bounds__(NW * 64, 1) void refine_grad_kernel(RefineArgs a) {
   for (; tile < ntiles; tile += stride) {
     const RefIn<D> cur = nx;
     refine_load<D>(a, tile + stride, r, E, nx);          // prefetch (clamped past the end)
+    // no live edge (every env of the tile masked out): nothing to evaluate. One scalar branch on
+    // the ballot for the whole wave -- no MFMA below runs under a lane-divergent condition.
+    if (__ballot(cur.in) == 0ull) continue;
     const float eye = (cur.in && cur.j == cur.i) ? 1.f : 0.f;
     const float d = sqrtf(sqsum<D>(cur.rp) + a.dist_eps);
     const float dfeat = cur.in ? d - a.dist_thr : 0.f;
@@ -282,6 +292,7 @@ __global__ __launch_bounds__(256) void refine_update_kernel(RefineArgs a) {
   const int l = threadIdx.x % RG;
   const int N = a.N, K = a.K, NK = N * K;
   const int b = (int)(node / N), i = (int)(node % N);
+  if (a.env_active && a.env_active[b] == 0) return;        // masked-out env: delta stays zero (whole group)
   const float* dE = a.dEv + (size_t)b * NK * D;
   float g[D];
 #pragma unroll

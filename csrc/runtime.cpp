@@ -533,10 +533,11 @@ class BpttDriver {
 // stream. The pointers and sizes are validated once; the control words (2 per iteration) are
 // cleared here; nothing is allocated or built; no host synchronisation -- the early-out lives in the
 // kernels. hn_out / flag_out (optional) receive the first iteration's h(s') and hinge flags.
+// env_active (optional, (B,) bytes on the device) is handed to the kernels as it is: never read here.
 int refine_loop(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, int B, int N, int Nn, int K, u64 wpack,
                 int f_bwd, u64 wrm, u64 wvec, u64 dEv, u64 ptr, u64 edges, u64 ctl, int loops, float dt, float dt_alpha,
-                float lr, float obs_r, float dist_thr, float dist_eps, u64 hn_out, u64 flag_out, int num_blocks,
-                int prec, u64 stream) {
+                float lr, float obs_r, float dist_thr, float dist_eps, u64 hn_out, u64 flag_out, u64 env_active,
+                int num_blocks, int prec, u64 stream) {
   if (dim != 2 && dim != 3) return -1;
   if (B < 1 || N < 1 || Nn < N || K < 1 || K > 16 || loops < 0 || num_blocks < 1 || f_bwd < 0 || s_env < Nn) return -1;
   if (prec < 0 || prec > 2) return -1;
@@ -550,6 +551,7 @@ int refine_loop(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, in
   r.wpack = P<const h16>(wpack); r.f_bwd = f_bwd; r.wrm = P<const h16>(wrm); r.wvec = P<const float>(wvec);
   r.dEv = P<float>(dEv); r.ptr = P<const int>(ptr); r.edges = P<const int>(edges);
   r.ctl = P<unsigned long long>(ctl);
+  r.env_active = P<const uint8_t>(env_active);
   r.dt = dt; r.dt_alpha = dt_alpha; r.lr = lr; r.obs_r = obs_r; r.dist_thr = dist_thr; r.dist_eps = dist_eps;
   const hipError_t e = hipMemsetAsync(r.ctl, 0, (size_t)loops * 2 * sizeof(unsigned long long), st);
   if (e != hipSuccess) return (int)e;

@@ -98,6 +98,14 @@ class TrainConfig:
     obstacle_points: int = 12
     cbf_dedup: bool = True            # HIP, BPTT: evaluate h'(s_{t+1}) through the next step's h of the
                                       # same neighbour pair (~1.08 E instead of 2 E CBF evaluations)
+    # validation during training (macbf_gnn_amd/validate.py); everything is off with val_every = 0
+    val_every: int = 0                # closed-loop validation every this many iterations (0: never)
+    val_envs: int = 4                 # held-out scenes per rank, fixed for the whole run
+    val_refine: bool = True           # also run the rollout with the CBF safety filter
+    val_refine_loops: int = REFINE_LOOPS
+    save_best: bool = False           # keep <model_path>.best (+ .best.json) at the best validation so far
+    best_metric: str = ""             # a val_*_rate key, higher is better; "": val_refined_safety_rate
+                                      # (val_safety_rate with val_refine off)
 
     def k_eff(self) -> int:
         return min(self.num_agents, self.top_k)

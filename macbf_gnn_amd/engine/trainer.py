@@ -11,11 +11,15 @@ tqdm, no logging/ckpt). Here one ``train_step`` is::
 
 ``engine`` is the HIP engine on a GPU (native kernels, no autograd) or the pure-torch
 oracle engine on CPU.
+
+With ``cfg.val_every > 0`` ``fit`` also validates every that many iterations: closed-loop
+episodes on held-out scenes, with and without the CBF safety filter (``macbf_gnn_amd/validate.py``),
+one extra JSON line per validation, and with ``cfg.save_best`` the checkpoint of the best one.
 """
 from __future__ import annotations
 
+import json
 import os
-
 import time
 from typing import Optional
 
@@ -80,6 +84,12 @@ class Trainer:
             self.gscale_dev = torch.full((1,), float(cfg.loss_scale_init), dtype=torch.float32, device=self.device)
             self._good_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._next = None
+        self.validator = None             # built by the first validate()
+        self._best = None                 # save_best: value of <model_path>.best, first read from its sidecar
+        self._best_read = False
+        if cfg.val_every or cfg.save_best:
+            from .. import validate as V
+            V.check_config(cfg)
         # the next iteration's scenarios on a side stream, launched as soon as enqueued: it runs in
         # the idle issue slots of the current iteration's CBF backward (inline sampling and a side
         # stream gated on the enqueued work both measured slower, docs/PERF.md round 5)
@@ -252,10 +262,75 @@ class Trainer:
             if self.cfg.model_path and (self.step_count % max(self.cfg.save_steps, 1)) == 0:
                 ckpt.save(self, self.cfg.model_path)
                 self.dp.barrier()
+            if self.cfg.val_every > 0 and (self.step_count % self.cfg.val_every) == 0:
+                self._validate_and_log()
         if self.cfg.model_path and steps > 0 and (self.step_count % max(self.cfg.save_steps, 1)) != 0:
             ckpt.save(self, self.cfg.model_path)      # final state of the run
             self.dp.barrier()
         return last
+
+    # ------------------------------------------------------------------ validation
+    def validate(self):
+        """Closed-loop validation of the current networks on the run's held-out scenes
+        (``macbf_gnn_amd/validate.py``) -> the ``val_*`` dict, identical on every rank. The
+        ``Validator`` (and its scenes) is built by the first call."""
+        if self.validator is None:
+            from ..validate import Validator
+            self.validator = Validator(self.cfg, self.device, self.dp)
+        return self.validator.validate(self.controller, self.cbf)
+
+    def _validate_and_log(self):
+        """One validation inside ``fit``: its JSON line (rank 0: stdout and log_path), the best
+        checkpoint, and its wall time taken out of the logger's throughput window."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)       # the training work so far is not validation time
+        t0 = time.perf_counter()
+        out = self.validate()
+        rec = {"step": self.step_count, **out}
+        if self.dp.rank == 0:
+            line = json.dumps(rec)
+            print(line, file=self.logger.stream, flush=True)
+            if self.cfg.log_path:
+                with open(self.cfg.log_path, "a") as f:
+                    f.write(line + "\n")
+        if self.cfg.save_best:
+            self._save_best(out)
+        self.logger.t0 += time.perf_counter() - t0
+        return rec
+
+    def best_path(self):
+        return self.cfg.model_path + ".best"
+
+    def _save_best(self, out):
+        """<model_path>.best (the ``ckpt.save`` format) + <model_path>.best.json {step, metric, value},
+        replaced on a strict improvement only. The sidecar of an earlier run of the same metric
+        is the starting point, so a resumed run does not overwrite a better file with a worse one."""
+        from ..validate import better, default_best_metric
+        metric = default_best_metric(self.cfg)
+        side = self.best_path() + ".json"
+        if not self._best_read:
+            self._best_read = True
+            found = float("-inf")
+            if self.dp.rank == 0 and _exists(side) and _exists(self.best_path()):
+                try:
+                    with open(side) as f:
+                        d = json.load(f)
+                    if d.get("metric") == metric:
+                        found = float(d["value"])
+                except (OSError, ValueError, KeyError, TypeError):
+                    pass
+            found = self.dp.max_scalar(found)          # rank 0's reading, on every rank
+            self._best = None if found == float("-inf") else found
+        value = float(out[metric])          # the dict is identical on every rank: so is the decision
+        if better(value, self._best):
+            self._best = value
+            ckpt.save(self, self.best_path())
+            if self.dp.rank == 0:
+                tmp = side + ".tmp"
+                with open(tmp, "w") as f:
+                    json.dump({"step": int(self.step_count), "metric": metric, "value": value}, f)
+                os.replace(tmp, side)
+            self.dp.barrier()
 
     def save(self, path):
         ckpt.save(self, path)

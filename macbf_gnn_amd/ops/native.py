@@ -830,7 +830,7 @@ def refine_grid(E: int, device, prec_code: int) -> int:
 
 
 def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl, *, loops, lr,
-           prec=None, hn_out=None, flag_out=None, num_blocks=None):
+           prec=None, hn_out=None, flag_out=None, num_blocks=None, env_active=None):
     """The safety-filter loop (csrc/refine.hip + the driver in csrc/runtime.cpp): ``loops`` gradient
     steps of ``delta`` (B, N, D), in place, on sum_e relu(-(h(s') - h + dt alpha h)) with
     s' = s + dt [v, a + delta].
@@ -841,7 +841,10 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
     (B, N*K) the reverse CSR of idx (``rev_csr``); ctl int64, >= 2*loops words, cleared by the
     driver: ctl[2 it] = edges with a non-zero hinge gradient in iteration it, ctl[2 it + 1] = the
     violation sum of iteration it times FX_VIOL. hn_out (B, N, K) fp32 / flag_out (B, N, K) uint8
-    (optional): h(s') and the hinge flags of the first iteration. No host synchronisation.
+    (optional): h(s') and the hinge flags of the first iteration. env_active (B,) bool / uint8 on the
+    device (optional): envs with 0 are left out -- their delta stays zero, they write no dEv / trace
+    and ctl counts the other envs alone; None is every env. The mask is read by the kernels only.
+    No host synchronisation.
     fp32 (x3) and bf16 builds; fp16 is not supported (the -1 upstream gradient has no loss scaling)."""
     if S is None or S.dim() != 3:
         raise NativeError("S must be (B, Nn, 4|8) node records")
@@ -885,6 +888,12 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
     check(wrm, wpack.dtype, (_planes(code) * (128 * 68 + 64 * 148),), "wrm")
     check(hn_out, torch.float32, (B, N, K), "hn_out")
     check(flag_out, torch.uint8, (B, N, K), "flag_out")
+    if env_active is not None:
+        if not isinstance(env_active, torch.Tensor) or env_active.dtype not in (torch.bool, torch.uint8):
+            raise NativeError("env_active must be a bool or uint8 tensor")
+        check(env_active, env_active.dtype, (B,), "env_active")
+        if env_active.dtype == torch.bool:
+            env_active = env_active.view(torch.uint8)         # same bytes, 0 / 1
     E = B * N * K
     if E >= 2 ** 31 - 2 ** 21:
         raise NativeError("too many edges for 32-bit indexing")
@@ -895,7 +904,7 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
                            ptr(wrm), ptr(wvec), ptr(dEv), ptr(rptr), ptr(redges), ptr(ctl), loops,
                            float(C.TIME_STEP), float(C.TIME_STEP * C.ALPHA_CBF), float(lr), float(C.OBS_RADIUS),
                            float(C.DIST_MIN_THRES), float(C.CBF_DIST_EPS_COORD * D), ptr(hn_out), ptr(flag_out),
-                           nb, code, stream_handle())
+                           ptr(env_active), nb, code, stream_handle())
     _ok(rc, "refine")
     return nb
 

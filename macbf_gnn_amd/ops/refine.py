@@ -10,6 +10,11 @@
 and inside the radius at s' -- outside it h(s') is 0 whatever the action); once an iteration has
 none, the remaining launches return at once and the actions stay as they are. ``viol`` is the
 hinge sum at the last evaluated iterate, as ``refine_actions`` reports it.
+
+``env_active`` (B,) bool / uint8 on the device masks whole envs out of a batch (episodes that are
+already over): their actions come back unchanged, and ``used`` / ``viol`` / the counts are those
+of the remaining envs, bit for bit what the filter gives on that sub-batch alone. The mask is read
+by the kernels; the host never looks at it.
 """
 from __future__ import annotations
 
@@ -21,12 +26,14 @@ from .packing import module_pack
 
 
 def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_LOOPS,
-                  lr: float = C.REFINE_LEARNING_RATE, return_trace: bool = False):
+                  lr: float = C.REFINE_LEARNING_RATE, return_trace: bool = False, *, env_active=None,
+                  num_blocks=None):
     """s (B, N, 2D), a (B, N, D), idx (B, N, K) on the HIP device, obstacles (B, M, D) or None ->
     (a_refined (B, N, D), used, viol); ``used`` (int64) and ``viol`` (float64) are 0-d device
     tensors -- the caller decides when to read them. ``return_trace=True`` appends a dict with the
     per-iteration active-edge counts ``counts`` (loops,), and ``hn`` (B, N, K) / ``active`` (B, N, K)
-    bool of the first iteration (tests)."""
+    bool of the first iteration (tests). ``env_active`` (B,): envs with False / 0 are not refined
+    (module docstring); ``num_blocks`` overrides the workgroup count of the gradient kernel."""
     if not s.is_cuda:
         raise native.NativeError("the safety filter runs on the HIP device")
     if s.dim() != 3 or a.dim() != 3 or idx.dim() != 3:
@@ -67,7 +74,8 @@ def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_L
             native.rev_csr(idx32, rptr, redges, n_nodes=Nn)
             dEv = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
             native.refine(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, dEv, rptr, redges, ctl,
-                          loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags)
+                          loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags, env_active=env_active,
+                          num_blocks=num_blocks)
         counts = ctl[0:2 * loops:2]
         used = (counts > 0).sum()
         if loops > 0:

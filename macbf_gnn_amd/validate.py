@@ -1,0 +1,202 @@
+"""Validation during training: closed-loop episodes on held-out scenes, with and without the CBF
+safety filter.
+
+The training log shows the open-loop statistics of the training rollouts. What a user picks a
+checkpoint by is the closed-loop behaviour: how safe the controller is on its own, and how safe
+and how far-reaching it is with the trained CBF as a test-time filter. ``Validator`` measures both
+on ``val_envs`` scenes per rank that are sampled once, from a seed stream of their own, and kept on
+the device for the whole run, so successive validations are comparable.
+
+Per ``validate(controller, cbf)`` two rollouts run from those scenes: nominal (controller only) and
+filtered (skipped with ``val_refine=False``). The metric definitions are those of
+``evaluate.rollout_eval`` (safety on s_{t+1} of the envs active at step t, reaching at the episode's
+end, ``max_steps = inner_loops``, stop when every env is done), with one deliberate difference: an
+env whose episode is over is no longer refined, it takes the controller's action. On a HIP device
+that is the per-env mask of the device-resident filter (``ops.refine.safety_filter(...,
+env_active=active)``); on CPU ``evaluate.refine_actions`` runs on the active sub-batch.
+
+Everything is counted on the device in integers. The host looks at the "all done" flag every
+``CHECK_EVERY`` steps and reads the totals once; a step that runs after every env is done changes
+neither the counts nor the states, so the result does not depend on that period. The count vectors
+are summed over the DP ranks before any ratio is taken: every rank returns the same dict.
+
+Precision (HIP): the networks run at the training ``dtype``. The filter has no fp16 build (its -1
+upstream gradient has no loss scaling), so a run that trains in fp16 validates both networks in
+bf16. ``validate`` puts ``mfma_dtype`` and the train / eval mode of both modules back, draws from
+no torch RNG, and uses none of the training engine's buffers, graphs or prefetched samples.
+"""
+from __future__ import annotations
+
+import time
+from typing import Dict, Optional
+
+import torch
+
+from . import config as C
+from .evaluate import MFMA_DTYPES, _euler, _knn, _safe_count, refine_actions
+
+VAL_SALT = 0x56414C5345454453          # the validation scenes' seed stream: _mix(cfg.seed, VAL_SALT)
+CHECK_EVERY = 5                        # rollout steps between host reads of the "all done" flag
+DIST_FX = float(1 << 20)               # fixed-point scale of the goal-distance sum
+COUNTS = ("safe_agent_steps", "agent_steps", "reached_agents", "agents", "env_steps", "refine_iters", "steps",
+          "goal_dist_fx")
+RATE_KEYS = ("val_safety_rate", "val_reaching_rate", "val_refined_safety_rate", "val_refined_reaching_rate")
+_UNSET = object()
+
+
+def default_best_metric(cfg) -> str:
+    return cfg.best_metric or ("val_refined_safety_rate" if cfg.val_refine else "val_safety_rate")
+
+
+def check_config(cfg):
+    """The validation entries of a TrainConfig that cannot work, reported before the run starts."""
+    if cfg.val_every < 0 or cfg.val_envs < 1 or cfg.val_refine_loops < 0:
+        raise ValueError("val_every must be >= 0, val_envs >= 1 and val_refine_loops >= 0")
+    m = default_best_metric(cfg)
+    if m not in RATE_KEYS:
+        raise ValueError(f"best_metric must be one of {RATE_KEYS}, got {m!r}")
+    if not cfg.val_refine and "refined" in m:
+        raise ValueError(f"best_metric {m!r} needs the filtered rollout, which val_refine=False turns off")
+    if cfg.save_best and not cfg.model_path:
+        raise ValueError("save_best writes <model_path>.best: it needs model_path")
+    if cfg.save_best and cfg.val_every <= 0:
+        raise ValueError("save_best needs validation: set val_every > 0")
+
+
+def val_dtype(cfg) -> torch.dtype:
+    """MFMA operand precision of the validation rollouts on a HIP device: the training dtype, bf16
+    when that is fp16 (the filter refuses fp16, and both rollouts use one precision)."""
+    return torch.bfloat16 if cfg.dtype == "fp16" else MFMA_DTYPES[cfg.dtype]
+
+
+def metrics_from_counts(nom: Dict[str, int], ref: Optional[Dict[str, int]], num_agents: int) -> Dict[str, float]:
+    """The ``val_*`` ratios of the summed integer totals (``COUNTS``) of the nominal and, if it ran,
+    the filtered rollout."""
+    envs = max(nom["agents"] // max(num_agents, 1), 1)
+    out = {"val_safety_rate": nom["safe_agent_steps"] / max(nom["agent_steps"], 1),
+           "val_reaching_rate": nom["reached_agents"] / max(nom["agents"], 1),
+           "val_mean_goal_dist": nom["goal_dist_fx"] / DIST_FX / max(nom["agents"], 1),
+           "val_mean_T": nom["env_steps"] / envs}
+    if ref is not None:
+        out.update({"val_refined_safety_rate": ref["safe_agent_steps"] / max(ref["agent_steps"], 1),
+                    "val_refined_reaching_rate": ref["reached_agents"] / max(ref["agents"], 1),
+                    "val_refined_mean_T": ref["env_steps"] / envs,
+                    # filter iterations per rollout step of a rank's batch
+                    "val_refine_iters": ref["refine_iters"] / max(ref["steps"], 1)})
+    return out
+
+
+class Validator:
+    def __init__(self, cfg: C.TrainConfig, device: torch.device, dp=None):
+        from .ops import scenario
+        self.cfg = cfg
+        self.device = device
+        self.dp = dp
+        rank = dp.rank if dp is not None else 0
+        s0, g, obs = scenario.generate(cfg.val_envs, cfg.num_agents, seed=scenario._mix(cfg.seed, VAL_SALT),
+                                       iteration=0, rank=rank, device=device, dim=cfg.dim,
+                                       num_obstacles=cfg.num_obstacles, obstacle_points=cfg.obstacle_points)
+        self.s0 = s0.to(device).clone()
+        self.g = g.to(device).clone()
+        self.obs = None if obs is None else obs.to(device).clone()
+        self.max_steps = int(cfg.inner_loops)
+        self.last_counts: Dict[str, Dict[str, int]] = {}      # the summed integer totals behind the last dict
+
+    # ------------------------------------------------------------------ one rollout
+    def _filter(self, cbf, s, a, idx, active):
+        cfg = self.cfg
+        if s.is_cuda:
+            from .ops import refine as refine_ops
+            a, used, _ = refine_ops.safety_filter(cbf, s, a, idx, obstacles=self.obs, loops=cfg.val_refine_loops,
+                                                  lr=C.REFINE_LEARNING_RATE, env_active=active)
+            return a, used
+        if not bool(active.any()):
+            return a, 0
+        ar, it, _ = refine_actions(cbf, s[active], a[active], idx[active], cfg.val_refine_loops,
+                                   C.REFINE_LEARNING_RATE, obstacles=None if self.obs is None else self.obs[active])
+        a = a.clone()
+        a[active] = ar
+        return a, it
+
+    def rollout(self, controller, cbf, refine: bool) -> torch.Tensor:
+        """One batch of episodes from the fixed scenes -> this rank's totals, an int64 device vector
+        in the order of ``COUNTS``. No host read except the "all done" flag every CHECK_EVERY steps."""
+        s, g, obs = self.s0, self.g, self.obs
+        B, N, _ = s.shape
+        D = s.shape[-1] // 2
+        k = min(self.cfg.top_k, N)
+        dev = s.device
+        zero = lambda: torch.zeros((), dtype=torch.int64, device=dev)
+        safe_n, env_steps, iters, steps = zero(), zero(), zero(), zero()
+        active = torch.ones(B, dtype=torch.bool, device=dev)
+        for t in range(self.max_steps):
+            alive = active.any()                     # device flag: false -> this step changes nothing
+            idx = _knn(s, k, obs)
+            with torch.no_grad():
+                a = controller(s, g, idx=idx, obstacles=obs)
+            if refine:
+                a, used = self._filter(cbf, s, a, idx, active)
+                iters += used
+            with torch.no_grad():
+                s = torch.where(alive, _euler(s, a), s)
+                act = active.long()
+                safe_n += (_safe_count(s, obs).long() * act).sum()
+                env_steps += act.sum()
+                steps += alive.long()
+                dist = torch.linalg.vector_norm(s[..., :D] - g, dim=-1).mean(-1)
+                active = active & (dist >= C.DIST_MIN_CHECK)
+            if (t + 1) % CHECK_EVERY == 0 and not bool(active.any()):
+                break
+        with torch.no_grad():
+            d = torch.linalg.vector_norm(s[..., :D] - g, dim=-1)
+            reached = (d < C.DIST_MIN_CHECK).sum()
+            dist_fx = (d.double().sum() * DIST_FX).round().long()
+            agents = torch.full((), B * N, dtype=torch.int64, device=dev)
+            return torch.stack([safe_n, env_steps * N, reached, agents, env_steps, iters, steps, dist_fx])
+
+    # ------------------------------------------------------------------ both rollouts, all ranks
+    def _reduce(self, vec: torch.Tensor):
+        dp = self.dp
+        if dp is not None and dp.enabled:
+            on_dev = dp.backend == "nccl" and self.device.type == "cuda"
+            vec = vec.to(self.device if on_dev else "cpu")
+            dp.all_reduce_(vec)
+        return vec.cpu().tolist()
+
+    def validate(self, controller, cbf) -> Dict[str, float]:
+        cfg = self.cfg
+        cuda = self.device.type == "cuda"
+        if cuda:
+            torch.cuda.synchronize(self.device)      # the pending training work is not validation time
+        t0 = time.perf_counter()
+        mods = (controller, cbf)
+        modes = [m.training for m in mods]
+        dtypes = [m.__dict__.get("mfma_dtype", _UNSET) for m in mods]
+        try:
+            for m in mods:
+                m.eval()
+                if cuda:
+                    m.mfma_dtype = val_dtype(cfg)
+            vecs = [self.rollout(controller, cbf, refine=False)]
+            if cfg.val_refine:
+                vecs.append(self.rollout(controller, cbf, refine=True))
+        finally:
+            for m, mode, dt in zip(mods, modes, dtypes):
+                m.train(mode)
+                if dt is _UNSET:
+                    m.__dict__.pop("mfma_dtype", None)
+                else:
+                    m.mfma_dtype = dt
+        tot = self._reduce(torch.cat(vecs))          # one collective, one host read
+        n = len(COUNTS)
+        nom = dict(zip(COUNTS, (int(x) for x in tot[:n])))
+        ref = dict(zip(COUNTS, (int(x) for x in tot[n:2 * n]))) if cfg.val_refine else None
+        self.last_counts = {"nominal": nom} if ref is None else {"nominal": nom, "refined": ref}
+        out = metrics_from_counts(nom, ref, cfg.num_agents)
+        out["val_ms"] = (time.perf_counter() - t0) * 1e3
+        return out
+
+
+def better(value: float, best: Optional[float]) -> bool:
+    """Strict improvement (higher is better)."""
+    return best is None or value > best

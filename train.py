@@ -5,6 +5,8 @@
 plus the knobs of SURVEY 5.6. Data parallel: launch one process per GPU with
 ``python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...``;
 each rank trains ``--num_envs`` environments and gradients are all-reduced over RCCL.
+``--val_every K`` adds a closed-loop validation on held-out scenes every K iterations (one extra
+JSON line, with and without the CBF safety filter); ``--save_best`` keeps ``<model_path>.best``.
 """
 from __future__ import annotations
 
@@ -41,6 +43,15 @@ def parse_args(argv=None):
     p.add_argument("--num_obstacles", type=int, default=0, help="static point-set obstacles per env")
     p.add_argument("--graph", action="store_true",
                    help="HIP: replay each iteration as captured graphs (launch-bound small configs)")
+    p.add_argument("--val_every", type=int, default=0,
+                   help="closed-loop validation on held-out scenes every this many iterations (0: off)")
+    p.add_argument("--val_envs", type=int, default=None, help="validation scenes per rank")
+    p.add_argument("--no_val_refine", action="store_true", help="validate the controller only (no safety filter)")
+    p.add_argument("--val_refine_loops", type=int, default=None)
+    p.add_argument("--save_best", action="store_true",
+                   help="keep <model_path>.best at the best validation value of --best_metric")
+    p.add_argument("--best_metric", type=str, default="",
+                   help="val_*_rate key to keep the best checkpoint by (default: val_refined_safety_rate)")
     return p.parse_args(argv)
 
 
@@ -51,8 +62,10 @@ def build_config(args):
                         reuse_nbr_idx=not args.no_reuse_nbr_idx,
                         alternate_every=args.alternate_every, early_stop=not args.no_early_stop,
                         model_path=args.model_path, log_path=args.log_path, dim=args.dim,
-                        num_obstacles=args.num_obstacles, graph=args.graph)
-    for name in ("train_steps", "inner_loops", "top_k", "lr", "display_steps", "save_steps"):
+                        num_obstacles=args.num_obstacles, graph=args.graph, val_every=args.val_every,
+                        val_refine=not args.no_val_refine, save_best=args.save_best, best_metric=args.best_metric)
+    for name in ("train_steps", "inner_loops", "top_k", "lr", "display_steps", "save_steps", "val_envs",
+                 "val_refine_loops"):
         v = getattr(args, name)
         if v is not None:
             setattr(cfg, name, v)
