@@ -224,6 +224,17 @@ struct RefineArgs {
   const uint8_t* env_active;
 };
 
+// Persistent safety filter for small envs (refine.hip refine_small_kernel): one workgroup per env
+// runs all `loops` iterations in one launch; r.dEv, r.ctl and r.it are not used.
+struct RefineSmallArgs {
+  RefineArgs r;
+  int loops;
+  // per-env result words (B, loops, 2), zero at the launch, plain stores: ew[b][it][0] = the env's
+  // edges with a non-zero hinge gradient in iteration it (zero from the env's stop on),
+  // ew[b][it][1] = its violation sum * FX_VIOL (after the stop: the value of the stopping iteration)
+  unsigned long long* ew;
+};
+
 // Deduplication of the h / h' evaluations (dedup.hip). h'(s_{t+1}) of slot (t,b,i,k) is the
 // same function value as h(s_{t+1}) of the slot (t+1,b,i,k') with the same neighbour, so only
 // the unmatched pairs ("extras") need their own evaluation.
@@ -450,6 +461,9 @@ int mb_refine_prepare(int dim);
 int mb_refine_prepare_f16(int dim);
 int mb_refine_prepare_x3(int dim);
 int mb_refine_update(const mb::RefineArgs* a, hipStream_t st);
+int mb_refine_small(const mb::RefineSmallArgs* a, hipStream_t st);
+int mb_refine_small_f16(const mb::RefineSmallArgs* a, hipStream_t st);
+int mb_refine_small_x3(const mb::RefineSmallArgs* a, hipStream_t st);
 int mb_rev_csr(const mb::CsrArgs* a, hipStream_t st);
 int mb_cbf_match(const mb::CbfMatchArgs* a, hipStream_t st);
 int mb_cbf_dh(const mb::CbfDhArgs* a, int num_blocks, hipStream_t st);

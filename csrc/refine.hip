@@ -22,6 +22,9 @@
 // (wave-uniform: tiles straddle envs whenever N*K is no multiple of 32), and the update leaves the
 // env's delta at zero. The control words then count the other envs alone, so a batch stops when
 // its live envs are clean, exactly as the filter run on those envs alone would.
+// Small envs (at most 64 graph nodes): refine_small_kernel runs the whole loop of an env in one
+// workgroup and one launch, with the same per-tile body (refine_tile) and the same update
+// (refine_node_grad, refine_step) on LDS copies, and per-env result words instead of atomics.
 #pragma clang fp contract(off)
 #include "common.h"
 #include "args.h"
@@ -48,9 +51,41 @@ struct RefIn {
   bool in;
 };
 
-// Edge e = (b*N + i)*K + k of a tile: every load is unconditional on a clamped index (idx holds
-// node ids up to Nn - 1, a / delta have N rows: an obstacle neighbour reads row N - 1 and is zeroed).
-// An edge of a masked-out env loads like any other and is then marked as not in the tile.
+// One edge (i, slot) of an env from the env's own arrays (global memory in refine_grad_kernel, the
+// LDS copies in refine_small_kernel): Sb the env's node records, ab / db its a / delta rows, jr the
+// neighbour slot, hv = h(s_t). Every load is unconditional on a clamped index (idx holds node ids
+// up to Nn - 1, a / delta have N rows: an obstacle neighbour reads row N - 1 and is zeroed). An edge
+// that is not in the tile (`in` false: past the end, or of a masked-out env) loads like any other.
+template <int D>
+DEV void refine_edge(const float4* Sb, const float* ab, const float* db, int jr, float hv, unsigned i, int N, int Nn,
+                     float dt, bool in, RefIn<D>& x) {
+  x.in = in;
+  const unsigned j = (unsigned)min(max(jr, 0), Nn - 1);
+  const bool agent_j = j < (unsigned)N;
+  const unsigned ja = agent_j ? j : (unsigned)(N - 1);
+  float pi[D], vi[D], pj[D], vj[D];
+  load_rec<D>(Sb, i, pi, vi);
+  load_rec<D>(Sb, j, pj, vj);
+  const float* ai = ab + (size_t)i * D;
+  const float* di = db + (size_t)i * D;
+  const float* aj = ab + (size_t)ja * D;
+  const float* dj = db + (size_t)ja * D;
+  x.hv = hv;
+#pragma unroll
+  for (int q = 0; q < D; ++q) {
+    const float ui = ai[q] + di[q];
+    const float uj = agent_j ? aj[q] + dj[q] : 0.f;
+    // s' = s + [v, a + delta] * dt (the evaluation's own expression order)
+    const float pin = pi[q] + vi[q] * dt, pjn = pj[q] + vj[q] * dt;
+    const float vin = vi[q] + ui * dt, vjn = vj[q] + uj * dt;
+    x.rp[q] = x.in ? pin - pjn : 0.f;
+    x.rv[q] = x.in ? vin - vjn : 0.f;
+  }
+  x.i = (int)i;
+  x.j = (int)j;
+}
+
+// Edge e = (b*N + i)*K + k of a batch-wide tile. An edge of a masked-out env is marked as not in the tile.
 template <int D>
 DEV void refine_load(const RefineArgs& a, unsigned tile, int r, unsigned E, RefIn<D>& x) {
   const unsigned e = tile * 32u + (unsigned)r;
@@ -58,33 +93,184 @@ DEV void refine_load(const RefineArgs& a, unsigned tile, int r, unsigned E, RefI
   const unsigned ec = inside ? e : 0u;
   const unsigned ik = ec / (unsigned)a.K;
   const unsigned b = ik / (unsigned)a.N;
-  x.in = inside && (a.env_active ? a.env_active[b] != 0 : true);
+  const bool in = inside && (a.env_active ? a.env_active[b] != 0 : true);
   const unsigned i = ik - b * (unsigned)a.N;
-  const int jr = a.idx[ec];
-  const unsigned j = (unsigned)min(max(jr, 0), a.Nn - 1);
-  const bool agent_j = j < (unsigned)a.N;
-  const unsigned ja = agent_j ? j : (unsigned)(a.N - 1);
-  const float4* Sb = a.S + (size_t)b * (size_t)a.s_env * REC<D>;
-  float pi[D], vi[D], pj[D], vj[D];
-  load_rec<D>(Sb, i, pi, vi);
-  load_rec<D>(Sb, j, pj, vj);
-  const float* ai = a.a + ((size_t)b * a.N + i) * D;
-  const float* di = a.delta + ((size_t)b * a.N + i) * D;
-  const float* aj = a.a + ((size_t)b * a.N + ja) * D;
-  const float* dj = a.delta + ((size_t)b * a.N + ja) * D;
-  x.hv = a.h[ec];
+  refine_edge<D>(a.S + (size_t)b * (size_t)a.s_env * REC<D>, a.a + (size_t)b * a.N * D, a.delta + (size_t)b * a.N * D,
+                 a.idx[ec], a.h[ec], i, a.N, a.Nn, a.dt, in, x);
+}
+
+// The weight images in LDS (the same layout in both kernels), copied by the whole workgroup; the
+// caller's barrier follows.
+struct RefW {
+  h16 *W2, *W3, *wf;                          // row-major W2 | W3, w1f (2 frags) | w1ft (4 frags)
+  float* vl;                                  // the side vector
+};
+DEV RefW refine_weights(unsigned char* smem, const RefineArgs& a) {
+  RefW w;
+  w.W2 = reinterpret_cast<h16*>(smem);
+  w.W3 = w.W2 + RM_W2;
+  w.wf = w.W2 + RMP;
+  w.vl = reinterpret_cast<float*>(smem + REFINE_W_BYTES);
+  block_copy16(w.W2, a.wrm, RMP * 2, false);
+  block_copy16(w.wf, a.wpack + (size_t)a.f_bwd * FRAG_ELEMS, 2 * FRAG_SZ, false);
+  block_copy16(w.wf + 2 * FRAG_ELEMS, a.wpack + (size_t)(a.f_bwd + 66) * FRAG_ELEMS, 4 * FRAG_SZ, false);
+  block_copy16(w.vl, a.wvec, CBF_VEC * 4);
+  return w;
+}
+
+// What one 32-edge tile gives per edge (lanes h = 0 and h = 1 of an edge hold the same values)
+template <int D>
+struct RefOut {
+  float hnv;            // radius-masked h(s')
+  float deriv;          // h(s') - h + dt alpha h
+  bool on;              // the hinge gradient is on
+  float gv[D];          // velocity rows of dL/d(s'_i - s'_j), before the self-edge / inactive zeroing
+};
+
+// violation term relu(-deriv) in fixed point; NaN / Inf / out of range -> FX_SAT
+DEV unsigned long long refine_viol_fx(float deriv) {
+  const float v = deriv < 0.f ? -deriv : (deriv == deriv ? 0.f : __builtin_inff());
+  const double xq = (double)v * FX_VIOL;
+  return (xq >= 0.0 && xq < FX_SAT) ? (unsigned long long)__double2ll_rn(xq) : (unsigned long long)FX_SAT;
+}
+
+// The per-tile body of both kernels, one wave, every lane: forward chain, fp32 head, hinge choice
+// and the data-path backward of the 32 edges in `cur`. Edges that are not in the tile (cur.in
+// false) ride along as zeros -- no MFMA here is under a lane-divergent condition.
+template <int D>
+DEV void refine_tile(const RefIn<D>& cur, const RefW& w, const RefineArgs& a, int lane, int h, RefOut<D>& o) {
+  const h16 *W2 = w.W2, *W3 = w.W3, *wf = w.wf;
+  const float* vl = w.vl;
+  const float eye = (cur.in && cur.j == cur.i) ? 1.f : 0.f;
+  const float d = sqrtf(sqsum<D>(cur.rp) + a.dist_eps);
+  const float dfeat = cur.in ? d - a.dist_thr : 0.f;
+  const bool mask = cur.in && d <= a.obs_r;             // radius mask at s'
+  const h16x8 F = cbf_edge_frag<D>(cur.rp, cur.rv, eye, dfeat, cur.in, h);
+  const h16* wt = wf + opaque_zero();
+  const h16* W2c = W2 + opaque_zero();
+  const h16* W3c = W3 + opaque_zero();
+  const float* vlc = vl + opaque_zero();
+  const float* b2 = vlc;
+  const float* b3 = vlc + 128;
+  const float* w4 = vlc + 192;
+  // ---- forward (the recompute chain of cbf_bwd_kernel / cbf_hfwd_kernel)
+  Pk H1b[2], H2b[4];
+  f32x16 H3p[2];
 #pragma unroll
-  for (int q = 0; q < D; ++q) {
-    const float ui = ai[q] + di[q];
-    const float uj = agent_j ? aj[q] + dj[q] : 0.f;
-    // s' = s + [v, a + delta] * dt (the evaluation's own expression order)
-    const float pin = pi[q] + vi[q] * a.dt, pjn = pj[q] + vj[q] * a.dt;
-    const float vin = vi[q] + ui * a.dt, vjn = vj[q] + uj * a.dt;
-    x.rp[q] = x.in ? pin - pjn : 0.f;
-    x.rv[q] = x.in ? vin - vjn : 0.f;
+  for (int mt = 0; mt < 2; ++mt) {
+    const f32x16 t1 = mma_bx(frag_fr(wt, mt, lane), F, zero16());
+    H1b[mt] = to_pk_relu(t1);
   }
-  x.i = (int)i;
-  x.j = (int)j;
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    f32x16 t2 = bias_rows4(b2, 32 * mt, h);
+    static_for<4>([&](auto kk_) {
+      constexpr int kk = decltype(kk_)::value;
+      t2 = mma(wrm_acc_fr(W2c, WS2, 32 * mt, kk, lane, RM_LO), pk_fr<kk & 1>(H1b[kk >> 1]), t2);
+    });
+    H2b[mt] = to_pk_relu(t2);
+  }
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) {
+    f32x16 t3 = bias_rows4(b3, 32 * mt, h);
+    static_for<8>([&](auto kk_) {
+      constexpr int kk = decltype(kk_)::value;
+      t3 = mma(wrm_acc_fr(W3c, WS3, 32 * mt, kk, lane, RM_LO), pk_fr<kk & 1>(H2b[kk >> 1]), t3);
+    });
+    relu_(t3);                                   // relu(H3) in fp32 (the head is fp32)
+    H3p[mt] = t3;
+  }
+  // ---- fp32 head, hinge choice
+  f32x2 hs2 = {0.f, 0.f};
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 w = *reinterpret_cast<const float4*>(w4 + 32 * mt + 8 * g + 4 * h);
+      hs2 = __builtin_elementwise_fma(f32x2{w.x, w.y}, f32x2{H3p[mt][4 * g], H3p[mt][4 * g + 1]}, hs2);
+      hs2 = __builtin_elementwise_fma(f32x2{w.z, w.w}, f32x2{H3p[mt][4 * g + 2], H3p[mt][4 * g + 3]}, hs2);
+    }
+  float hs = hs2.x + hs2.y;
+  hs += shfl_xor32(hs);
+  const float hnv = mask ? hs + vlc[256] : 0.f;
+  const float hv = cur.hv;
+  const float deriv = hnv - hv + a.dt_alpha * hv;          // cbf_fwd_kernel's expression order
+  // the hinge gradient is on where the condition is violated and h(s') is inside the radius
+  // (outside it h(s') = 0 whatever the action)
+  const bool on = mask && deriv < 0.f;
+  const float dhv = on ? -1.f : 0.f;                       // d relu(-deriv) / d h(s')
+  o.hnv = hnv;
+  o.deriv = deriv;
+  o.on = on;
+  // ---- head backward: dH3pre = w4 * dh . relu'(H3)
+  Pk d3b[2], H3b[2];
+  const f32x2 dh2 = {dhv, dhv};
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) {
+    f32x16 d3;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 w = *reinterpret_cast<const float4*>(w4 + 32 * mt + 8 * g + 4 * h);
+      const f32x2 lo = f32x2{w.x, w.y} * dh2, hi = f32x2{w.z, w.w} * dh2;
+      d3[4 * g] = lo.x; d3[4 * g + 1] = lo.y; d3[4 * g + 2] = hi.x; d3[4 * g + 3] = hi.y;
+    }
+    H3b[mt] = to_pk(H3p[mt]);
+    d3b[mt] = to_pk(d3);
+    mask_pk(d3b[mt], H3b[mt]);
+  }
+  // ---- dH2pre = (W3^T dH3pre) . relu'(H2)
+  Pk d2b[4];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    f32x16 t = zero16();
+    static_for<4>([&](auto kk_) {
+      constexpr int kk = decltype(kk_)::value;
+      t = mma(wrmT_acc_fr(W3c, WS3, 32 * mt, kk, lane, RM_LO), pk_fr<kk & 1>(d3b[kk >> 1]), t);
+    });
+    d2b[mt] = to_pk(t);
+    mask_pk(d2b[mt], H2b[mt]);
+  }
+  // ---- dH1pre = (W2^T dH2pre) . relu'(H1)
+  Pk d1b[2];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) {
+    f32x16 t = zero16();
+    static_for<8>([&](auto kk_) {
+      constexpr int kk = decltype(kk_)::value;
+      t = mma(wrmT_acc_fr(W2c, WS2, 32 * mt, kk, lane, RM_LO), pk_fr<kk & 1>(d2b[kk >> 1]), t);
+    });
+    d1b[mt] = to_pk(t);
+    mask_pk(d1b[mt], H1b[mt]);
+  }
+  // ---- dF = W1^T dH1pre (rows: s_i - s_j (0..2D-1), eye, dist) -> velocity rows D..2D-1
+  {
+    f32x16 t = zero16();
+    static_for<4>([&](auto kk_) {
+      constexpr int kk = decltype(kk_)::value;
+      t = mma(frag_fr(wt, 2 + kk, lane), pk_fr<kk & 1>(d1b[kk >> 1]), t);
+    });
+    // lane h = 0 holds rows 0..3 in regs 0..3, lane h = 1 rows 4..7
+    float g4[8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { g4[q] = t[q]; g4[4 + q] = shfl_xor32(t[q]); }
+#pragma unroll
+    for (int q = 0; q < D; ++q) o.gv[q] = g4[D + q];
+  }
+}
+
+// What lane h = 0 of an edge in the tile records: the violation term and the active count (per-lane
+// integers), the optional trace at the batch-wide edge index et, and the edge's dEv record at dE.
+template <int D>
+DEV void refine_record(const RefIn<D>& cur, const RefOut<D>& o, float* hn_out, uint8_t* flag_out, size_t et, float* dE,
+                       unsigned long long& nact, unsigned long long& vsum) {
+  vsum += refine_viol_fx(o.deriv);
+  nact += o.on ? 1ull : 0ull;
+  if (hn_out) hn_out[et] = o.hnv;
+  if (flag_out) flag_out[et] = o.on ? 1 : 0;
+  // self edges: s'_i - s'_i = 0 whatever the action; inactive edges: exact zeros
+  const bool wr = o.on && cur.j != cur.i;
+#pragma unroll
+  for (int q = 0; q < D; ++q) dE[q] = wr ? o.gv[q] : 0.f;
 }
 
 template <int NW, int D>
@@ -93,14 +279,7 @@ __global__ __launch_bounds__(NW * 64, 1) void refine_grad_kernel(RefineArgs a) {
   // iteration's control words stay zero, which stops the next one)
   if (a.it > 0 && a.ctl[2 * (a.it - 1)] == 0ull) return;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  h16* W2 = reinterpret_cast<h16*>(smem);
-  h16* W3 = W2 + RM_W2;
-  h16* wf = W2 + RMP;                         // w1f (2 frags) | w1ft (4 frags)
-  float* vl = reinterpret_cast<float*>(smem + REFINE_W_BYTES);
-  block_copy16(W2, a.wrm, RMP * 2, false);
-  block_copy16(wf, a.wpack + (size_t)a.f_bwd * FRAG_ELEMS, 2 * FRAG_SZ, false);
-  block_copy16(wf + 2 * FRAG_ELEMS, a.wpack + (size_t)(a.f_bwd + 66) * FRAG_ELEMS, 4 * FRAG_SZ, false);
-  block_copy16(vl, a.wvec, CBF_VEC * 4);
+  const RefW w = refine_weights(smem, a);
   __syncthreads();
   const int wave = wave_id(), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const unsigned E = (unsigned)a.B * a.N * a.K;
@@ -116,133 +295,11 @@ __global__ __launch_bounds__(NW * 64, 1) void refine_grad_kernel(RefineArgs a) {
     // no live edge (every env of the tile masked out): nothing to evaluate. One scalar branch on
     // the ballot for the whole wave -- no MFMA below runs under a lane-divergent condition.
     if (__ballot(cur.in) == 0ull) continue;
-    const float eye = (cur.in && cur.j == cur.i) ? 1.f : 0.f;
-    const float d = sqrtf(sqsum<D>(cur.rp) + a.dist_eps);
-    const float dfeat = cur.in ? d - a.dist_thr : 0.f;
-    const bool mask = cur.in && d <= a.obs_r;             // radius mask at s'
-    const h16x8 F = cbf_edge_frag<D>(cur.rp, cur.rv, eye, dfeat, cur.in, h);
-    const h16* wt = wf + opaque_zero();
-    const h16* W2c = W2 + opaque_zero();
-    const h16* W3c = W3 + opaque_zero();
-    const float* vlc = vl + opaque_zero();
-    const float* b2 = vlc;
-    const float* b3 = vlc + 128;
-    const float* w4 = vlc + 192;
-    // ---- forward (the recompute chain of cbf_bwd_kernel / cbf_hfwd_kernel)
-    Pk H1b[2], H2b[4];
-    f32x16 H3p[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      const f32x16 t1 = mma_bx(frag_fr(wt, mt, lane), F, zero16());
-      H1b[mt] = to_pk_relu(t1);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      f32x16 t2 = bias_rows4(b2, 32 * mt, h);
-      static_for<4>([&](auto kk_) {
-        constexpr int kk = decltype(kk_)::value;
-        t2 = mma(wrm_acc_fr(W2c, WS2, 32 * mt, kk, lane, RM_LO), pk_fr<kk & 1>(H1b[kk >> 1]), t2);
-      });
-      H2b[mt] = to_pk_relu(t2);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      f32x16 t3 = bias_rows4(b3, 32 * mt, h);
-      static_for<8>([&](auto kk_) {
-        constexpr int kk = decltype(kk_)::value;
-        t3 = mma(wrm_acc_fr(W3c, WS3, 32 * mt, kk, lane, RM_LO), pk_fr<kk & 1>(H2b[kk >> 1]), t3);
-      });
-      relu_(t3);                                   // relu(H3) in fp32 (the head is fp32)
-      H3p[mt] = t3;
-    }
-    // ---- fp32 head, hinge choice
-    f32x2 hs2 = {0.f, 0.f};
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 w = *reinterpret_cast<const float4*>(w4 + 32 * mt + 8 * g + 4 * h);
-        hs2 = __builtin_elementwise_fma(f32x2{w.x, w.y}, f32x2{H3p[mt][4 * g], H3p[mt][4 * g + 1]}, hs2);
-        hs2 = __builtin_elementwise_fma(f32x2{w.z, w.w}, f32x2{H3p[mt][4 * g + 2], H3p[mt][4 * g + 3]}, hs2);
-      }
-    float hs = hs2.x + hs2.y;
-    hs += shfl_xor32(hs);
-    const float hnv = mask ? hs + vlc[256] : 0.f;
-    const float hv = cur.hv;
-    const float deriv = hnv - hv + a.dt_alpha * hv;          // cbf_fwd_kernel's expression order
-    // the hinge gradient is on where the condition is violated and h(s') is inside the radius
-    // (outside it h(s') = 0 whatever the action)
-    const bool on = mask && deriv < 0.f;
-    const float dhv = on ? -1.f : 0.f;                       // d relu(-deriv) / d h(s')
+    RefOut<D> o;
+    refine_tile<D>(cur, w, a, lane, h, o);
     if (cur.in && h == 0) {
-      const unsigned e = tile * 32u + (unsigned)r;
-      // violation term relu(-deriv) in fixed point; NaN / Inf / out of range -> FX_SAT
-      const float v = deriv < 0.f ? -deriv : (deriv == deriv ? 0.f : __builtin_inff());
-      const double xq = (double)v * FX_VIOL;
-      vsum += (xq >= 0.0 && xq < FX_SAT) ? (unsigned long long)__double2ll_rn(xq) : (unsigned long long)FX_SAT;
-      nact += on ? 1ull : 0ull;
-      if (a.hn_out) a.hn_out[e] = hnv;
-      if (a.flag_out) a.flag_out[e] = on ? 1 : 0;
-    }
-    // ---- head backward: dH3pre = w4 * dh . relu'(H3)
-    Pk d3b[2], H3b[2];
-    const f32x2 dh2 = {dhv, dhv};
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      f32x16 d3;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 w = *reinterpret_cast<const float4*>(w4 + 32 * mt + 8 * g + 4 * h);
-        const f32x2 lo = f32x2{w.x, w.y} * dh2, hi = f32x2{w.z, w.w} * dh2;
-        d3[4 * g] = lo.x; d3[4 * g + 1] = lo.y; d3[4 * g + 2] = hi.x; d3[4 * g + 3] = hi.y;
-      }
-      H3b[mt] = to_pk(H3p[mt]);
-      d3b[mt] = to_pk(d3);
-      mask_pk(d3b[mt], H3b[mt]);
-    }
-    // ---- dH2pre = (W3^T dH3pre) . relu'(H2)
-    Pk d2b[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      f32x16 t = zero16();
-      static_for<4>([&](auto kk_) {
-        constexpr int kk = decltype(kk_)::value;
-        t = mma(wrmT_acc_fr(W3c, WS3, 32 * mt, kk, lane, RM_LO), pk_fr<kk & 1>(d3b[kk >> 1]), t);
-      });
-      d2b[mt] = to_pk(t);
-      mask_pk(d2b[mt], H2b[mt]);
-    }
-    // ---- dH1pre = (W2^T dH2pre) . relu'(H1)
-    Pk d1b[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      f32x16 t = zero16();
-      static_for<8>([&](auto kk_) {
-        constexpr int kk = decltype(kk_)::value;
-        t = mma(wrmT_acc_fr(W2c, WS2, 32 * mt, kk, lane, RM_LO), pk_fr<kk & 1>(d2b[kk >> 1]), t);
-      });
-      d1b[mt] = to_pk(t);
-      mask_pk(d1b[mt], H1b[mt]);
-    }
-    // ---- dF = W1^T dH1pre (rows: s_i - s_j (0..2D-1), eye, dist) -> velocity rows D..2D-1
-    {
-      f32x16 t = zero16();
-      static_for<4>([&](auto kk_) {
-        constexpr int kk = decltype(kk_)::value;
-        t = mma(frag_fr(wt, 2 + kk, lane), pk_fr<kk & 1>(d1b[kk >> 1]), t);
-      });
-      // lane h = 0 holds rows 0..3 in regs 0..3, lane h = 1 rows 4..7
-      float g4[8];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { g4[q] = t[q]; g4[4 + q] = shfl_xor32(t[q]); }
-      if (cur.in && h == 0) {
-        const unsigned e = tile * 32u + (unsigned)r;
-        // self edges: s'_i - s'_i = 0 whatever the action; inactive edges: exact zeros
-        const bool wr = on && cur.j != cur.i;
-        float* o = a.dEv + (size_t)e * D;
-#pragma unroll
-        for (int q = 0; q < D; ++q) o[q] = wr ? g4[D + q] : 0.f;
-      }
+      const size_t e = tile * 32u + (unsigned)r;
+      refine_record<D>(cur, o, a.hn_out, a.flag_out, e, a.dEv + e * D, nact, vsum);
     }
   }
   const unsigned long long n = wave_sum_u64(nact), s = wave_sum_u64(vsum);
@@ -250,6 +307,140 @@ __global__ __launch_bounds__(NW * 64, 1) void refine_grad_kernel(RefineArgs a) {
     if (n) atomicAdd(a.ctl + 2 * a.it, n);
     if (s) atomicAdd(a.ctl + 2 * a.it + 1, s);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Persistent filter for small envs (Nn <= SMALL_MAXN graph nodes, K <= 16: at most 32 tiles): one
+// workgroup per env runs the whole loop in one launch. Prologue: the weight images and the env's
+// own data (node records, a, delta = 0, h(s_t), idx, reverse CSR) go to LDS; dEv lives in LDS.
+// Iteration: the waves split the env's tiles (env-local: edge e of the env is in tile e / 32) and
+// run refine_tile on `a + delta` from LDS -> barrier -> the env's active count and violation sum
+// (integers, summed over the waves in LDS) go to ew[b, it] as plain stores of one lane -> the
+// 16-lane-group update of refine_update on the LDS copies -> barrier. The env stops at its first
+// iteration without an active edge (a zero hinge has a zero gradient: delta can never change
+// again): the later violation words are filled with that iteration's sum -- exact, the iterate
+// stays as it is -- and the later counts stay zero. The stop is read from LDS after a barrier and
+// made scalar, so every wave runs the same barriers; no workgroup waits for another. An env with
+// env_active[b] == 0 returns at once: ew[b] and its delta stay zero. No atomics.
+constexpr int RS_MAXN = 64;                    // SMALL_MAXN (ops/native.py)
+constexpr int RS_MAXE = RS_MAXN * 16;          // edges of the largest env
+constexpr int RS_PTR = 68;                     // Nn + 1 reverse-CSR offsets, padded to 16 B
+template <int D> constexpr size_t RS_S_OFF = REFINE_LDS;                                     // node records
+template <int D> constexpr size_t RS_A_OFF = RS_S_OFF<D> + (size_t)RS_MAXN * REC<D> * 16;    // a | delta
+template <int D> constexpr size_t RS_H_OFF = RS_A_OFF<D> + (size_t)2 * RS_MAXN * D * 4;      // h(s_t)
+template <int D> constexpr size_t RS_I_OFF = RS_H_OFF<D> + (size_t)RS_MAXE * 4;              // idx
+template <int D> constexpr size_t RS_E_OFF = RS_I_OFF<D> + (size_t)RS_MAXE * 4;              // reverse-CSR edges
+template <int D> constexpr size_t RS_P_OFF = RS_E_OFF<D> + (size_t)RS_MAXE * 4;              // reverse-CSR offsets
+template <int D> constexpr size_t RS_G_OFF = RS_P_OFF<D> + (size_t)RS_PTR * 4;               // dEv
+template <int D> constexpr size_t RS_R_OFF = RS_G_OFF<D> + (size_t)RS_MAXE * D * 4;          // per-wave sums
+template <int NW, int D> constexpr size_t REFINE_SMALL_LDS = RS_R_OFF<D> + (size_t)NW * 2 * 8;
+static_assert(REFINE_LDS % 16 == 0 && REFINE_SMALL_LDS<REFINE_NW, 3> <= 128 * 1024, "LDS layout");
+
+// The update of both paths, lane l of agent i's 16-lane group: g = sum_out dEv - sum_in dEv over
+// one env's arrays (dE (N*K, D), ptr / edges its reverse CSR), the same value in all 16 lanes.
+// Outgoing edges: one coalesced segment of K records; incoming: the reverse CSR over the lanes;
+// then the fixed xor butterfly.
+template <int D>
+DEV void refine_node_grad(const float* dE, const int* ptr, const int* edges, int i, int l, int K, int NK, float (&g)[D]) {
+#pragma unroll
+  for (int q = 0; q < D; ++q) g[q] = 0.f;
+  for (int k = l; k < K; k += RG)
+#pragma unroll
+    for (int q = 0; q < D; ++q) g[q] += dE[((size_t)i * K + k) * D + q];
+  const int q0 = min(max(ptr[i], 0), NK), q1 = min(max(ptr[i + 1], 0), NK);
+  for (int x = q0 + l; x < q1; x += RG) {
+    const int e = min(max(edges[x], 0), NK - 1);
+#pragma unroll
+    for (int q = 0; q < D; ++q) g[q] -= dE[(size_t)e * D + q];
+  }
+#pragma unroll
+  for (int q = 0; q < D; ++q) g[q] = grp_sum(g[q]);
+}
+// the gradient step of one delta component: d s'_v / d delta = dt
+DEV float refine_step(float d, float lr, float dt, float g) { return d - lr * (dt * g); }
+
+template <int NW, int D>
+__global__ __launch_bounds__(NW * 64, 1) void refine_small_kernel(RefineSmallArgs sa) {
+  const RefineArgs& a = sa.r;
+  const int b = blockIdx.x;
+  if (a.env_active && a.env_active[b] == 0) return;        // masked-out env: nothing is written
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const RefW w = refine_weights(smem, a);
+  float4* Sl = reinterpret_cast<float4*>(smem + RS_S_OFF<D>);
+  float* al = reinterpret_cast<float*>(smem + RS_A_OFF<D>);
+  float* dl = al + RS_MAXN * D;
+  float* hl = reinterpret_cast<float*>(smem + RS_H_OFF<D>);
+  int* il = reinterpret_cast<int*>(smem + RS_I_OFF<D>);
+  int* el = reinterpret_cast<int*>(smem + RS_E_OFF<D>);
+  int* pl = reinterpret_cast<int*>(smem + RS_P_OFF<D>);
+  float* gl = reinterpret_cast<float*>(smem + RS_G_OFF<D>);
+  unsigned long long* red = reinterpret_cast<unsigned long long*>(smem + RS_R_OFF<D>);
+  const int N = a.N, Nn = a.Nn, K = a.K, NK = N * K;
+  const int tid = threadIdx.x, nthr = NW * 64;
+  {
+    const float4* Sg = a.S + (size_t)b * (size_t)a.s_env * REC<D>;
+    for (int x = tid; x < Nn * REC<D>; x += nthr) Sl[x] = Sg[x];
+    const float* ag = a.a + (size_t)b * N * D;
+    for (int x = tid; x < N * D; x += nthr) { al[x] = ag[x]; dl[x] = 0.f; }
+    const float* hg = a.h + (size_t)b * NK;
+    const int* ig = a.idx + (size_t)b * NK;
+    const int* eg = a.edges + (size_t)b * NK;
+    for (int x = tid; x < NK; x += nthr) { hl[x] = hg[x]; il[x] = ig[x]; el[x] = eg[x]; }
+    const int* pg = a.ptr + (size_t)b * (Nn + 1);
+    for (int x = tid; x <= Nn; x += nthr) pl[x] = pg[x];
+  }
+  __syncthreads();
+  const int wave = wave_id(), lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const unsigned ntiles = ((unsigned)NK + 31u) / 32u;
+  unsigned long long* ew = sa.ew + (size_t)b * sa.loops * 2;
+  for (int it = 0; it < sa.loops; ++it) {
+    // ---- gradient phase: tiles wave, wave + NW, ... (a scalar trip count per wave)
+    unsigned long long nact = 0, vsum = 0;
+    for (unsigned tile = (unsigned)wave; tile < ntiles; tile += NW) {
+      const unsigned e = tile * 32u + (unsigned)r;
+      const bool inside = e < (unsigned)NK;
+      const unsigned ec = inside ? e : 0u;
+      RefIn<D> cur;
+      refine_edge<D>(Sl, al, dl, il[ec], hl[ec], ec / (unsigned)K, N, Nn, a.dt, inside, cur);
+      RefOut<D> o;
+      refine_tile<D>(cur, w, a, lane, h, o);
+      if (cur.in && h == 0) {
+        const bool tr = it == 0;
+        refine_record<D>(cur, o, tr ? a.hn_out : nullptr, tr ? a.flag_out : nullptr, (size_t)b * NK + e,
+                         gl + (size_t)e * D, nact, vsum);
+      }
+    }
+    const unsigned long long n = wave_sum_u64(nact), s = wave_sum_u64(vsum);
+    if (lane == 0) { red[2 * wave] = n; red[2 * wave + 1] = s; }
+    __syncthreads();
+    unsigned long long act = 0, vs = 0;
+#pragma unroll
+    for (int x = 0; x < NW; ++x) { act += red[2 * x]; vs += red[2 * x + 1]; }
+    if (tid == 0) { ew[2 * it] = act; ew[2 * it + 1] = vs; }
+    // the same value in every lane of the workgroup; made scalar so the loop stays wave-uniform
+    const bool more = __builtin_amdgcn_readfirstlane((int)(act != 0ull)) != 0;
+    if (!more) {
+      if (tid == 0)
+        for (int x = it + 1; x < sa.loops; ++x) ew[2 * x + 1] = vs;
+      break;
+    }
+    // ---- update phase: one 16-lane group per agent, agents grp, grp + NW*4, ... (the trip count
+    // is the same for every lane; a group past the end redoes agent N - 1 and writes nothing)
+    const int l = tid % RG, grp = tid / RG;
+    for (int i0 = 0; i0 < N; i0 += nthr / RG) {
+      const int i = min(i0 + grp, N - 1);
+      float g[D];
+      refine_node_grad<D>(gl, pl, el, i, l, K, NK, g);
+      if (l == 0 && i0 + grp < N) {
+        float* d = dl + (size_t)i * D;
+#pragma unroll
+        for (int q = 0; q < D; ++q) d[q] = refine_step(d[q], a.lr, a.dt, g[q]);
+      }
+    }
+    __syncthreads();
+  }
+  float* dg = a.delta + (size_t)b * N * D;
+  for (int x = tid; x < N * D; x += nthr) dg[x] = dl[x];
 }
 
 template <int D>
@@ -280,6 +471,28 @@ extern "C" int MB_SYM(refine_grad)(const mb::RefineArgs* a, int num_blocks, hipS
   return (int)hipGetLastError();
 }
 
+// The persistent filter of envs of at most RS_MAXN graph nodes: one launch of B workgroups. Sets
+// the kernel's dynamic-LDS attribute itself; ew (B, loops, 2) must be zero at the launch.
+extern "C" int MB_SYM(refine_small)(const mb::RefineSmallArgs* sa, hipStream_t st) {
+  using namespace mb;
+  using namespace mb::MB_PREC;
+  const RefineArgs* a = &sa->r;
+  if (a->K > 16 || a->K < 1 || a->B < 1 || a->N < 1 || a->Nn < a->N || a->Nn > RS_MAXN || sa->loops < 1) return -1;
+  if (!a->S || !a->idx || !a->a || !a->delta || !a->h || !a->wpack || !a->wrm || !a->wvec || !a->ptr || !a->edges ||
+      !sa->ew)
+    return -2;
+  if (a->s_env < a->Nn) return -1;
+  auto go = [&](auto kern, size_t lds) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kern, dim3(a->B), dim3(REFINE_NW * 64), lds, st, *sa);
+    return (int)hipGetLastError();
+  };
+  if (a->dim == 3) return go(refine_small_kernel<REFINE_NW, 3>, REFINE_SMALL_LDS<REFINE_NW, 3>);
+  if (a->dim == 2) return go(refine_small_kernel<REFINE_NW, 2>, REFINE_SMALL_LDS<REFINE_NW, 2>);
+  return -1;
+}
+
 #if !MB_X3 && !MB_FP16
 // The update is plain fp32: compiled once (with the default build of this file).
 namespace mb {
@@ -293,29 +506,13 @@ __global__ __launch_bounds__(256) void refine_update_kernel(RefineArgs a) {
   const int N = a.N, K = a.K, NK = N * K;
   const int b = (int)(node / N), i = (int)(node % N);
   if (a.env_active && a.env_active[b] == 0) return;        // masked-out env: delta stays zero (whole group)
-  const float* dE = a.dEv + (size_t)b * NK * D;
   float g[D];
-#pragma unroll
-  for (int q = 0; q < D; ++q) g[q] = 0.f;
-  // outgoing edges: one coalesced segment of K records; incoming: the reverse CSR over the lanes
-  for (int k = l; k < K; k += RG)
-#pragma unroll
-    for (int q = 0; q < D; ++q) g[q] += dE[((size_t)i * K + k) * D + q];
-  const int* ptr = a.ptr + (size_t)b * (a.Nn + 1);
-  const int* edges = a.edges + (size_t)b * NK;
-  const int q0 = min(max(ptr[i], 0), NK), q1 = min(max(ptr[i + 1], 0), NK);
-  for (int x = q0 + l; x < q1; x += RG) {
-    const int e = min(max(edges[x], 0), NK - 1);
-#pragma unroll
-    for (int q = 0; q < D; ++q) g[q] -= dE[(size_t)e * D + q];
-  }
-#pragma unroll
-  for (int q = 0; q < D; ++q) g[q] = grp_sum(g[q]);
+  MB_PREC::refine_node_grad<D>(a.dEv + (size_t)b * NK * D, a.ptr + (size_t)b * (a.Nn + 1), a.edges + (size_t)b * NK, i, l,
+                               K, NK, g);
   if (l != 0) return;
-  // d s'_v / d delta = dt
   float* d = a.delta + ((size_t)b * N + i) * D;
 #pragma unroll
-  for (int q = 0; q < D; ++q) d[q] = d[q] - a.lr * (a.dt * g[q]);
+  for (int q = 0; q < D; ++q) d[q] = MB_PREC::refine_step(d[q], a.lr, a.dt, g[q]);
 }
 
 }  // namespace mb

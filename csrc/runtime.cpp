@@ -570,10 +570,40 @@ int refine_loop(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, in
   return 0;
 }
 
+// Persistent safety filter for small envs (csrc/refine.hip refine_small_kernel): the whole loop of
+// every env in ONE launch on the caller's stream, one workgroup per env. The pointers and sizes are
+// validated once; the kernel's dynamic-LDS attribute is set by its launcher; nothing is allocated
+// or cleared here (delta and ew (B, loops, 2) arrive zeroed); no host synchronisation.
+int refine_small(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, int B, int N, int Nn, int K, u64 wpack,
+                 int f_bwd, u64 wrm, u64 wvec, u64 ptr, u64 edges, u64 ew, int loops, float dt, float dt_alpha,
+                 float lr, float obs_r, float dist_thr, float dist_eps, u64 hn_out, u64 flag_out, u64 env_active,
+                 int prec, u64 stream) {
+  if (dim != 2 && dim != 3) return -1;
+  if (B < 1 || N < 1 || Nn < N || K < 1 || K > 16 || loops < 0 || f_bwd < 0 || s_env < Nn) return -1;
+  if (Nn > 64) return -4;                                      // SMALL_MAXN: the env must fit one workgroup's LDS
+  if (prec < 0 || prec > 2) return -1;
+  if (!S || !idx || !a || !delta || !h || !wpack || !wrm || !wvec || !ptr || !edges || !ew) return -2;
+  if (loops == 0) return 0;
+  mb::RefineSmallArgs sa{};
+  mb::RefineArgs& r = sa.r;
+  r.S = P<const float4>(S); r.s_env = s_env; r.dim = dim; r.idx = P<const int>(idx);
+  r.a = P<const float>(a); r.delta = P<float>(delta); r.h = P<const float>(h);
+  r.B = B; r.N = N; r.Nn = Nn; r.K = K;
+  r.wpack = P<const h16>(wpack); r.f_bwd = f_bwd; r.wrm = P<const h16>(wrm); r.wvec = P<const float>(wvec);
+  r.ptr = P<const int>(ptr); r.edges = P<const int>(edges);
+  r.env_active = P<const uint8_t>(env_active);
+  r.dt = dt; r.dt_alpha = dt_alpha; r.lr = lr; r.obs_r = obs_r; r.dist_thr = dist_thr; r.dist_eps = dist_eps;
+  r.hn_out = P<float>(hn_out); r.flag_out = P<uint8_t>(flag_out);     // the kernel writes them at iteration 0 only
+  sa.loops = loops;
+  sa.ew = P<unsigned long long>(ew);
+  return (prec == 2 ? mb_refine_small_x3 : prec == 1 ? mb_refine_small_f16 : mb_refine_small)(&sa, ST(stream));
+}
+
 }  // namespace
 
 void register_runtime(py::module& m) {
   m.def("refine_loop", &refine_loop);
+  m.def("refine_small", &refine_small);
   py::class_<BpttDriver>(m, "BpttDriver")
       .def(py::init<py::dict>())
       .def("run", &BpttDriver::run, py::arg("T"), py::arg("act_coef"), py::arg("stream"), py::arg("use_acts") = false);

@@ -22,6 +22,7 @@ removed (their decision is the code's default, the measurement is in docs/PERF.m
 | MACBF_OVERLAP_HFWD | by size | engine/hip_engine.py | 1 / 0: CBF h of each step's main slots on a side stream during the rollout (default: on for fp32 ranks of 12,288-24,576 agents, off otherwise; A/B) |
 | MACBF_GRAPH_LAUNCH | 1 | engine/hip_engine.py | small scenes: the rollout driver launches the horizon's backward graph itself (0: replay from Python, A/B) |
 | MACBF_PUBLISH | 1 | engine/hip_engine.py | early stop through a queue marker instead of kernel publication (tests) |
+| MACBF_REFINE_SMALL | by size and precision | ops/refine.py | safety filter with `impl=None`: 1 the persistent one-launch kernel on eligible scenes (at most 64 graph nodes per env), 0 the launch loop (tests/test_gpu_refine_small.py, A/B) |
 | MACBF_SELFCHECK | 1 | ops/selfcheck.py | skip the start-up self-check of the 16x16x32 kernels |
 | MACBF_ARCH | gfx950 | csrc/build.py | build target |
 """

@@ -829,23 +829,10 @@ def refine_grid(E: int, device, prec_code: int) -> int:
     return max(1, min((tiles + waves - 1) // waves, num_cu(device)))
 
 
-def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl, *, loops, lr,
-           prec=None, hn_out=None, flag_out=None, num_blocks=None, env_active=None):
-    """The safety-filter loop (csrc/refine.hip + the driver in csrc/runtime.cpp): ``loops`` gradient
-    steps of ``delta`` (B, N, D), in place, on sum_e relu(-(h(s') - h + dt alpha h)) with
-    s' = s + dt [v, a + delta].
-
-    S (B, Nn, 4|8) node records of s_t (agents first); idx (B, N, K) int32 into the Nn nodes;
-    a / delta (B, N, D) fp32 contiguous; h (B, N, K) the radius-masked h(s_t); wpack / wrm / wvec the
-    packed CBF weights (``module_pack``); dEv (B, N, K, D) workspace; rptr (B, Nn+1) / redges
-    (B, N*K) the reverse CSR of idx (``rev_csr``); ctl int64, >= 2*loops words, cleared by the
-    driver: ctl[2 it] = edges with a non-zero hinge gradient in iteration it, ctl[2 it + 1] = the
-    violation sum of iteration it times FX_VIOL. hn_out (B, N, K) fp32 / flag_out (B, N, K) uint8
-    (optional): h(s') and the hinge flags of the first iteration. env_active (B,) bool / uint8 on the
-    device (optional): envs with 0 are left out -- their delta stays zero, they write no dEv / trace
-    and ctl counts the other envs alone; None is every env. The mask is read by the kernels only.
-    No host synchronisation.
-    fp32 (x3) and bf16 builds; fp16 is not supported (the -1 upstream gradient has no loss scaling)."""
+def _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec, hn_out, flag_out,
+                 env_active):
+    """The argument validation shared by ``refine`` and ``refine_small`` ->
+    (B, N, Nn, K, D, loops, precision code, env_active as uint8)."""
     if S is None or S.dim() != 3:
         raise NativeError("S must be (B, Nn, 4|8) node records")
     B, Nn, W = S.shape
@@ -863,18 +850,14 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
         if t is None:
             raise NativeError(f"{name} is required")
         check(t, torch.float32, (B, N, D), name)
-    if h is None or dEv is None or rptr is None or redges is None or ctl is None:
-        raise NativeError("h, dEv, rptr, redges and ctl are required")
+    if h is None or rptr is None or redges is None:
+        raise NativeError("h, rptr and redges are required")
     check(h, torch.float32, (B, N, K), "h")
-    check(dEv, torch.float32, (B, N, K, D), "dEv")
     check(rptr, torch.int32, (B, Nn + 1), "rptr")
     check(redges, torch.int32, (B, N * K), "redges")
     loops = int(loops)
     if loops < 0:
         raise NativeError("loops must be >= 0")
-    check(ctl, torch.int64, None, "ctl")
-    if ctl.dim() != 1 or ctl.numel() < 2 * loops:
-        raise NativeError(f"ctl must be int64 with at least 2*loops = {2 * loops} words, got {tuple(ctl.shape)}")
     code = _half(wpack, "wpack", prec)
     if code == 1:
         raise NativeError("safety filter: fp16 is not supported (the -1 upstream gradient has no loss scaling); "
@@ -894,6 +877,34 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
         check(env_active, env_active.dtype, (B,), "env_active")
         if env_active.dtype == torch.bool:
             env_active = env_active.view(torch.uint8)         # same bytes, 0 / 1
+    return B, N, Nn, K, D, loops, code, env_active
+
+
+def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl, *, loops, lr,
+           prec=None, hn_out=None, flag_out=None, num_blocks=None, env_active=None):
+    """The safety-filter loop (csrc/refine.hip + the driver in csrc/runtime.cpp): ``loops`` gradient
+    steps of ``delta`` (B, N, D), in place, on sum_e relu(-(h(s') - h + dt alpha h)) with
+    s' = s + dt [v, a + delta].
+
+    S (B, Nn, 4|8) node records of s_t (agents first); idx (B, N, K) int32 into the Nn nodes;
+    a / delta (B, N, D) fp32 contiguous; h (B, N, K) the radius-masked h(s_t); wpack / wrm / wvec the
+    packed CBF weights (``module_pack``); dEv (B, N, K, D) workspace; rptr (B, Nn+1) / redges
+    (B, N*K) the reverse CSR of idx (``rev_csr``); ctl int64, >= 2*loops words, cleared by the
+    driver: ctl[2 it] = edges with a non-zero hinge gradient in iteration it, ctl[2 it + 1] = the
+    violation sum of iteration it times FX_VIOL. hn_out (B, N, K) fp32 / flag_out (B, N, K) uint8
+    (optional): h(s') and the hinge flags of the first iteration. env_active (B,) bool / uint8 on the
+    device (optional): envs with 0 are left out -- their delta stays zero, they write no dEv / trace
+    and ctl counts the other envs alone; None is every env. The mask is read by the kernels only.
+    No host synchronisation.
+    fp32 (x3) and bf16 builds; fp16 is not supported (the -1 upstream gradient has no loss scaling)."""
+    if dEv is None or ctl is None:
+        raise NativeError("dEv and ctl are required")
+    B, N, Nn, K, D, loops, code, env_active = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges,
+                                                           loops, prec, hn_out, flag_out, env_active)
+    check(dEv, torch.float32, (B, N, K, D), "dEv")
+    check(ctl, torch.int64, None, "ctl")
+    if ctl.dim() != 1 or ctl.numel() < 2 * loops:
+        raise NativeError(f"ctl must be int64 with at least 2*loops = {2 * loops} words, got {tuple(ctl.shape)}")
     E = B * N * K
     if E >= 2 ** 31 - 2 ** 21:
         raise NativeError("too many edges for 32-bit indexing")
@@ -907,6 +918,67 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
                            ptr(env_active), nb, code, stream_handle())
     _ok(rc, "refine")
     return nb
+
+
+def refine_small_eligible(Nn: int, K: int) -> bool:
+    """Envs the persistent filter takes: at most SMALL_MAXN graph nodes (agents + obstacle points)
+    and K <= 16, so at most 32 tiles of 32 edges per env."""
+    return 1 <= Nn <= SMALL_MAXN and 1 <= K <= C.MAX_TOP_K
+
+
+def refine_small(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, ew, *, loops, lr,
+                 prec=None, hn_out=None, flag_out=None, env_active=None):
+    """The persistent safety filter of small envs (csrc/refine.hip refine_small_kernel): the whole
+    loop of ``refine`` in ONE launch, one workgroup per env, for envs of at most SMALL_MAXN graph
+    nodes. Arguments as for ``refine`` (no dEv: it lives in LDS), except the result words: ew
+    (B, loops, 2) int64, ZERO on entry (as is delta), ew[b, it, 0] = env b's edges with a non-zero
+    hinge gradient in iteration it, ew[b, it, 1] = its violation sum times FX_VIOL. An env stops at
+    its first iteration u without an active edge: its later counts stay zero and its later violation
+    words repeat the one of u (the iterate no longer changes). Envs with env_active 0 write nothing.
+    ``refine_reduce`` turns ew into the loop path's ``used`` / ``viol`` / ``counts``. No host
+    synchronisation. fp32 (x3) and bf16 builds; fp16 is not supported."""
+    # what needs no device first: the size limit, the precision, the loop count
+    if S is None or S.dim() != 3:
+        raise NativeError("S must be (B, Nn, 4|8) node records")
+    if S.shape[1] > SMALL_MAXN:
+        raise NativeError(f"the persistent filter takes envs of at most SMALL_MAXN = {SMALL_MAXN} graph nodes, "
+                          f"got {S.shape[1]}")
+    if _half(wpack, "wpack", prec) == 1:
+        raise NativeError("safety filter: fp16 is not supported (the -1 upstream gradient has no loss scaling); "
+                          "use fp32 or bf16")
+    if int(loops) < 0:
+        raise NativeError("loops must be >= 0")
+    if ew is None:
+        raise NativeError("ew is required")
+    B, N, Nn, K, D, loops, code, env_active = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges,
+                                                           loops, prec, hn_out, flag_out, env_active)
+    check(ew, torch.int64, (B, loops, 2), "ew")
+    rc = lib().refine_small(ptr(S), Nn, D, ptr(idx), ptr(a), ptr(delta), ptr(h), B, N, Nn, K, ptr(wpack), int(f_bwd),
+                            ptr(wrm), ptr(wvec), ptr(rptr), ptr(redges), ptr(ew), loops,
+                            float(C.TIME_STEP), float(C.TIME_STEP * C.ALPHA_CBF), float(lr), float(C.OBS_RADIUS),
+                            float(C.DIST_MIN_THRES), float(C.CBF_DIST_EPS_COORD * D), ptr(hn_out), ptr(flag_out),
+                            ptr(env_active), code, stream_handle())
+    _ok(rc, "refine_small")
+
+
+def refine_reduce(ew):
+    """ew (B, loops, 2) int64 per-env result words of ``refine_small`` -> (used, viol, counts) as the
+    loop path's control words give them, with tensor ops alone (nothing is read on the host):
+    counts[it] = sum_b ew[b, it, 0]; used = max_b #{it: ew[b, it, 0] != 0} -- the batch runs as long
+    as its slowest env; viol = sum_b ew[b, min(used, loops - 1), 1] / FX_VIOL, where an env that
+    stopped earlier contributes the (unchanged) violation of its stopping iteration. Integer sums:
+    exactly the loop path's values. loops = 0: (0, 0.0, empty)."""
+    if ew.dim() != 3 or ew.shape[-1] != 2 or ew.dtype != torch.int64:
+        raise NativeError("ew must be int64 (B, loops, 2)")
+    B, loops, _ = ew.shape
+    counts = ew[:, :, 0].sum(0)
+    if loops == 0 or B == 0:
+        return (torch.zeros((), dtype=torch.int64, device=ew.device),
+                torch.zeros((), dtype=torch.float64, device=ew.device), counts)
+    used = (ew[:, :, 0] != 0).sum(1).max()
+    last = torch.clamp(used, max=loops - 1).view(1)
+    viol = ew[:, :, 1].index_select(1, last).sum().double() / FX_VIOL
+    return used, viol, counts
 
 
 CTRL_EDGE_WAVES = 4          # csrc/ctrl.hip EB_WAVES

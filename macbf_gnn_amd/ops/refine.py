@@ -15,25 +15,60 @@ hinge sum at the last evaluated iterate, as ``refine_actions`` reports it.
 already over): their actions come back unchanged, and ``used`` / ``viol`` / the counts are those
 of the remaining envs, bit for bit what the filter gives on that sub-batch alone. The mask is read
 by the kernels; the host never looks at it.
+
+Two implementations, bit for bit the same results. ``"loop"``: ``loops`` x (refine_grad,
+refine_update) launches, any scene. ``"persistent"``: envs of at most ``native.SMALL_MAXN`` graph
+nodes run the whole loop in one launch, one workgroup per env (``refine_small_kernel``); each env
+stops on its own and reports per-env result words, which ``native.refine_reduce`` turns into the
+loop path's ``used`` / ``viol`` / counts on the device. ``impl=None`` chooses: ``MACBF_REFINE_SMALL``
+(0 / 1) if set, else the persistent kernel where it measured faster (``AUTO_PERSISTENT``: bf16 envs
+of at most 32 graph nodes; docs/PERF.md, "Persistent filter") and the loop everywhere else.
 """
 from __future__ import annotations
 
 import torch
 
 from .. import config as C
+from .. import knobs
 from . import graph, native
 from .packing import module_pack
 
 
+IMPLS = (None, "loop", "persistent")
+# impl=None: precision -> the largest env (graph nodes) for which the persistent kernel is the
+# default, i.e. where its minimum beat the loop path's by more than that path's spread
+# (docs/PERF.md, "Persistent filter"): bf16 at 32 nodes (0.50 against 0.71 ms per call); at 64 nodes
+# it is 5 % behind, and in fp32 (x3, 4 waves, three MFMAs per product) it is behind at every size.
+AUTO_PERSISTENT = {"bf16": 32}
+
+
+def choose_impl(impl, prec: str, Nn: int, K: int) -> str:
+    """"loop" or "persistent" for a scene of Nn graph nodes per env and K slots (module docstring).
+    An explicit "persistent" on a scene that is not eligible is an error, never a fall-back."""
+    if impl not in IMPLS:
+        raise native.NativeError(f"unknown safety-filter impl {impl!r} (None, 'loop' or 'persistent')")
+    ok = native.refine_small_eligible(Nn, K)
+    if impl == "persistent" and not ok:
+        raise native.NativeError(f"the persistent filter takes envs of at most {native.SMALL_MAXN} graph nodes and "
+                                 f"K <= {C.MAX_TOP_K} (got Nn = {Nn}, K = {K}); use impl='loop' or None")
+    if impl is not None:
+        return impl
+    forced = knobs.get_int("MACBF_REFINE_SMALL", -1)
+    if forced >= 0:
+        return "persistent" if forced and ok else "loop"
+    return "persistent" if ok and Nn <= AUTO_PERSISTENT.get(prec, 0) else "loop"
+
+
 def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_LOOPS,
                   lr: float = C.REFINE_LEARNING_RATE, return_trace: bool = False, *, env_active=None,
-                  num_blocks=None):
+                  num_blocks=None, impl=None):
     """s (B, N, 2D), a (B, N, D), idx (B, N, K) on the HIP device, obstacles (B, M, D) or None ->
     (a_refined (B, N, D), used, viol); ``used`` (int64) and ``viol`` (float64) are 0-d device
     tensors -- the caller decides when to read them. ``return_trace=True`` appends a dict with the
     per-iteration active-edge counts ``counts`` (loops,), and ``hn`` (B, N, K) / ``active`` (B, N, K)
     bool of the first iteration (tests). ``env_active`` (B,): envs with False / 0 are not refined
-    (module docstring); ``num_blocks`` overrides the workgroup count of the gradient kernel."""
+    (module docstring); ``num_blocks`` overrides the workgroup count of the loop path's gradient
+    kernel; ``impl`` None / "loop" / "persistent" (module docstring)."""
     if not s.is_cuda:
         raise native.NativeError("the safety filter runs on the HIP device")
     if s.dim() != 3 or a.dim() != 3 or idx.dim() != 3:
@@ -61,30 +96,43 @@ def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_L
         a32 = a.detach().float().contiguous()
         delta = torch.zeros_like(a32)
         h = torch.empty(1, B, N, K, dtype=torch.float32, device=dev)
-        ctl = torch.zeros(max(2 * loops, 2), dtype=torch.int64, device=dev)
+        persistent = choose_impl(impl, mp.prec, Nn, K) == "persistent"
         hn = flags = None
         if return_trace:
             hn = torch.zeros(B, N, K, dtype=torch.float32, device=dev)
             flags = torch.zeros(B, N, K, dtype=torch.uint8, device=dev)
+        ctl = ew = None
+        if persistent:
+            ew = torch.zeros(B, loops, 2, dtype=torch.int64, device=dev)
+        else:
+            ctl = torch.zeros(max(2 * loops, 2), dtype=torch.int64, device=dev)
         if loops > 0:
             native.cbf_fwd(S.view(1, *S.shape), idx32.view(1, B, N, K), w, mp.off["w1f"], v, two=False, h_out=h,
                            prec=mp.prec)
             rptr = torch.empty(B, Nn + 1, dtype=torch.int32, device=dev)
             redges = torch.empty(B, N * K, dtype=torch.int32, device=dev)
             native.rev_csr(idx32, rptr, redges, n_nodes=Nn)
-            dEv = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
-            native.refine(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, dEv, rptr, redges, ctl,
-                          loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags, env_active=env_active,
-                          num_blocks=num_blocks)
-        counts = ctl[0:2 * loops:2]
-        used = (counts > 0).sum()
-        if loops > 0:
-            # the violation of the last evaluated iterate: iteration `used` if it ran (it then counted
-            # no active edge), else the last one; selected on the device (no host read)
-            last = torch.clamp(used, max=loops - 1).view(1)
-            viol = ctl[1:2 * loops:2].index_select(0, last).view(()).double() / native.FX_VIOL
+            if persistent:
+                native.refine_small(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, rptr, redges, ew,
+                                    loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags,
+                                    env_active=env_active)
+            else:
+                dEv = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
+                native.refine(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, dEv, rptr, redges, ctl,
+                              loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags, env_active=env_active,
+                              num_blocks=num_blocks)
+        if persistent:
+            used, viol, counts = native.refine_reduce(ew)
         else:
-            viol = torch.zeros((), dtype=torch.float64, device=dev)
+            counts = ctl[0:2 * loops:2]
+            used = (counts > 0).sum()
+            if loops > 0:
+                # the violation of the last evaluated iterate: iteration `used` if it ran (it then counted
+                # no active edge), else the last one; selected on the device (no host read)
+                last = torch.clamp(used, max=loops - 1).view(1)
+                viol = ctl[1:2 * loops:2].index_select(0, last).view(()).double() / native.FX_VIOL
+            else:
+                viol = torch.zeros((), dtype=torch.float64, device=dev)
         out = (a32 + delta).to(a.dtype)
     if return_trace:
         return out, used, viol, {"counts": counts.clone(), "hn": hn, "active": flags.bool() if flags is not None else None}

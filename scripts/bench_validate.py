@@ -5,6 +5,8 @@
     python scripts/bench_validate.py mask     [--num_agents 1024] [--val_envs 4] [--dtype fp32]
                                               [--model_path checkpoints/headline_4k.pt] [--rounds 5]
                                               [--refine_loops 50]
+    python scripts/bench_validate.py impl     [--num_agents 32] [--val_envs 8] [--dtype bf16]
+                                              [--model_path checkpoints/cfg2_6k.pt] [--rounds 5]
 
 ``validate``: wall time of ``Validator.validate`` (both rollouts, the totals' read included), one
 warm-up call (scenes, packing tables) and ``--rounds`` timed ones.
@@ -14,6 +16,13 @@ warm-up call (scenes, packing tables) and ``--rounds`` timed ones.
 is run on those recorded steps with ``env_active=mask`` and with ``env_active=None``, interleaved
 round by round, each episode timed between device synchronisations. The first recorded step is
 then timed with B, B-1, .. 0 live envs (10 calls per reading, the minimum over the rounds).
+
+``impl``: the two implementations of the filter (``safety_filter(impl="loop" / "persistent")``) on
+a scene the persistent kernel takes (at most 64 graph nodes per env), interleaved round by round in
+one process: the filter alone on the recorded steps of one filtered episode (as ``mask`` does, with
+the recorded masks), and a whole ``validate()`` with ``MACBF_REFINE_SMALL`` forcing each path.
+Reports the minimum, the mean and the spread (max - min) over the rounds, and checks that both
+paths gave the same iteration count and the same validation counts.
 
 Prints one JSON line. Without ``--model_path`` the networks are random-initialised."""
 import argparse
@@ -58,7 +67,7 @@ def record_episode(v, ctrl, cbf, loops):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["validate", "mask"])
+    ap.add_argument("mode", choices=["validate", "mask", "impl"])
     ap.add_argument("--num_agents", type=int, default=1024)
     ap.add_argument("--val_envs", type=int, default=4)
     ap.add_argument("--dim", type=int, default=2)
@@ -86,6 +95,43 @@ def main():
         out.update({k: x for k, x in res.items() if k != "val_ms"})
         out.update({"val_ms": ms, "val_ms_min": min(ms), "val_ms_mean": sum(ms) / len(ms),
                     "counts": v.last_counts})
+    elif a.mode == "impl":
+        impls = ("loop", "persistent")
+        knob = {"loop": "0", "persistent": "1"}
+        val, counts = {n: [] for n in impls}, {}
+        for rnd in range(a.rounds + 1):                  # round 0 warms up
+            for name in impls:
+                os.environ["MACBF_REFINE_SMALL"] = knob[name]
+                ms = v.validate(ctrl, cbf)["val_ms"]
+                if rnd:
+                    val[name].append(ms)
+                counts[name] = v.last_counts
+        os.environ.pop("MACBF_REFINE_SMALL", None)
+        ctrl.eval(), cbf.eval()
+        ctrl.mfma_dtype = cbf.mfma_dtype = V.val_dtype(cfg)
+        rec = record_episode(v, ctrl, cbf, a.refine_loops)
+        times, iters = {n: [] for n in impls}, {}
+        for rnd in range(a.rounds + 1):
+            for name in impls:
+                used_sum = torch.zeros((), dtype=torch.int64, device=dev)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for s, act, idx, m in rec:
+                    _, used, _ = safety_filter(cbf, s, act, idx, obstacles=v.obs, loops=a.refine_loops, env_active=m,
+                                               impl=name)
+                    used_sum += used
+                torch.cuda.synchronize()
+                if rnd:
+                    times[name].append(1e3 * (time.perf_counter() - t0))
+                iters[name] = int(used_sum)
+        out.update({"steps": len(rec), "same_refine_iters": iters["loop"] == iters["persistent"],
+                    "same_val_counts": counts["loop"] == counts["persistent"], "refine_iters": iters["loop"]})
+        for name in impls:
+            for key, d in (("val_ms", val[name]), ("filter_episode_ms", times[name])):
+                out[f"{name}_{key}_min"] = min(d)
+                out[f"{name}_{key}_mean"] = sum(d) / len(d)
+                out[f"{name}_{key}_spread"] = max(d) - min(d)
+            out[f"{name}_filter_ms_per_step_min"] = min(times[name]) / max(len(rec), 1)
     else:
         ctrl.eval(), cbf.eval()
         ctrl.mfma_dtype = cbf.mfma_dtype = V.val_dtype(cfg)
