@@ -414,9 +414,35 @@ struct GradAssembleArgs {
   const float* sums; const float* counts; const float* local; float* row;   // row null: no stats
 };
 
+// Closed-loop episodes (episode.hip): the glue between the per-step kernels of a batch of episodes
+// (scan, controller, safety filter), all on one stream. Every count lives on the device.
+constexpr int EP_ALIVE = 0, EP_SAFE = 1, EP_ENV_STEPS = 2, EP_STEPS = 3, EP_ITERS = 4, EP_WORDS = 5;
+constexpr int EP_OUT = 8;                  // result words, the order of validate.COUNTS
+struct EpisodeArgs {
+  const float4* S_cur; float4* S_next; long s_env;   // node records of s_t / s_{t+1} (strides in records)
+  int dim, B, N;
+  const float* A;                          // (B,N,D) controller actions
+  float* delta;                            // (B,N,D) filter correction or null; zeroed once it is read
+  const float* G;                          // (B,N,D) goals
+  float dt;
+  long long* st;                           // EP_WORDS state words: alive flag and the running totals
+  unsigned long long* dist_fx;             // (B,) sum of |p' - g| * FX_DIST of the step, cleared by the tally
+  float* safe;                             // (B,) the scan's safe-agent counts of S_cur, cleared by the tally
+  uint8_t* active; uint8_t* prev_active;   // (B,) env still running / was running in the previous step
+  // the filter's result words of this step: mode 1 ctl (2 per iteration, refine_loop), mode 2 ew
+  // (B, loops, 2) of refine_small (cleared by the tally: the kernel wants them zero), mode 0 none
+  const unsigned long long* ctl; unsigned long long* ew; int loops, mode;
+  unsigned long long thr_fx;               // DIST_MIN_CHECK * N * FX_DIST
+  float thr;                               // DIST_MIN_CHECK
+  long long* out;                          // EP_OUT result words (episode_final)
+};
+
 }  // namespace mb
 
 extern "C" {
+int mb_episode_advance(const mb::EpisodeArgs* a, hipStream_t st);
+int mb_episode_tally(const mb::EpisodeArgs* a, hipStream_t st);
+int mb_episode_final(const mb::EpisodeArgs* a, hipStream_t st);
 int mb_scan(const mb::ScanArgs* a, hipStream_t st);
 int mb_scan_plan(const mb::ScanArgs* a, long* out);
 int mb_reduce_multi(const mb::ReduceMultiArgs* a, hipStream_t st);

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(HERE)
 PKG = os.path.join(ROOT, "macbf_gnn_amd")
 BUILD = os.path.join(ROOT, "build", "csrc")
 ARCH = os.environ.get("MACBF_ARCH", "gfx950")
-KERNELS = ["scan", "scenario", "ctrl", "cbf", "refine", "dedup", "graph", "optim"]
+KERNELS = ["scan", "scenario", "ctrl", "cbf", "refine", "episode", "dedup", "graph", "optim"]
 HALF_KERNELS = {"ctrl", "cbf", "refine"}       # compiled per MFMA operand precision (csrc/prec.h)
 
 

@@ -599,11 +599,215 @@ int refine_small(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, i
   return (prec == 2 ? mb_refine_small_x3 : prec == 1 ? mb_refine_small_f16 : mb_refine_small)(&sa, ST(stream));
 }
 
+// Closed-loop episode driver (csrc/episode.hip): a whole batch of episodes -- validation during
+// training, evaluation -- with or without the safety filter, as one call. Per step, on the caller's
+// stream: cell_sort + ONE scan of s_t (kNN and the safety count of the step before), the controller
+// forward, the filter (cbf_fwd for h(s_t), rev_csr, refine_loop or refine_small), episode_advance,
+// episode_tally, and a swap of the two record buffers. The buffers come from Python
+// (ops/episode.py), validated there once per call; nothing is allocated and the host does not wait
+// inside a step. Every check_every steps the "some env still runs" word is copied to pinned memory
+// and the stream is waited for; a step issued after every env finished changes nothing, so the
+// result does not depend on that period. After the loop: the safety-only scan of the final state
+// and episode_final.
+class EpisodeDriver {
+ public:
+  EpisodeDriver() {
+    chk(hipHostMalloc((void**)&alive_host_, sizeof(long long), hipHostMallocDefault), "hipHostMalloc");
+    *alive_host_ = 1;
+  }
+  ~EpisodeDriver() {
+    if (alive_host_) (void)hipHostFree(alive_host_);
+  }
+  EpisodeDriver(const EpisodeDriver&) = delete;
+  EpisodeDriver& operator=(const EpisodeDriver&) = delete;
+
+  struct Cfg {
+    int B, N, Nn, K, D, num_cu, prec_ctrl, prec_cbf, apw, max_steps, check_every;
+    int refine, persistent, loops, mask_done, cbf_blocks, refine_blocks;
+    int f_edge, f_node, f_cbf;
+    float L, r2_train, ttc_train, r2_check, ttc_check, dt, dt_alpha, lr, obs_r, sqrt3, dist_thr, dist_eps, done_thr;
+    u64 S0, S1, G, idx, A, pooled, argmax, perm, safe, st, dist_fx, active, prev_active, out;
+    u64 ctrl_w, ctrl_v, cbf_w, cbf_rm, cbf_v, delta, h, rptr, redges, csr_ws, dEv, ctl, ew, scan_ws;
+    long scan_ws_env;
+    mb::LossConsts lc;
+    u64 stream;
+  };
+
+  // Returns (steps issued, 0 or 1: the buffer that holds the final state).
+  std::pair<int, int> run(py::dict c) {
+    Cfg g = parse(c);
+    py::gil_scoped_release nogil;       // the loop waits for the stream every check_every steps
+    return loop(g);
+  }
+
+ private:
+  static Cfg parse(const py::dict& c) {
+    auto I = [&](const char* k) { return c[k].cast<long>(); };
+    auto F = [&](const char* k) { return c[k].cast<float>(); };
+    auto U = [&](const char* k) { return c[k].cast<u64>(); };
+    Cfg g{};
+    g.B = (int)I("B"); g.N = (int)I("N"); g.Nn = (int)I("Nn"); g.K = (int)I("K"); g.D = (int)I("D");
+    g.num_cu = (int)I("num_cu"); g.prec_ctrl = (int)I("prec_ctrl"); g.prec_cbf = (int)I("prec_cbf"); g.apw = (int)I("apw");
+    g.max_steps = (int)I("max_steps"); g.check_every = (int)I("check_every");
+    g.refine = (int)I("refine"); g.persistent = (int)I("persistent"); g.loops = (int)I("loops");
+    g.mask_done = (int)I("mask_done"); g.cbf_blocks = (int)I("cbf_blocks"); g.refine_blocks = (int)I("refine_blocks");
+    g.f_edge = (int)I("f_edge"); g.f_node = (int)I("f_node"); g.f_cbf = (int)I("f_cbf");
+    g.L = F("L"); g.r2_train = F("r2_train"); g.ttc_train = F("ttc_train"); g.r2_check = F("r2_check");
+    g.ttc_check = F("ttc_check"); g.dt = F("dt"); g.dt_alpha = F("dt_alpha"); g.lr = F("lr"); g.obs_r = F("obs_r");
+    g.sqrt3 = F("sqrt3"); g.dist_thr = F("dist_thr"); g.dist_eps = F("dist_eps"); g.done_thr = F("done_thr");
+    g.S0 = U("S0"); g.S1 = U("S1"); g.G = U("G"); g.idx = U("idx"); g.A = U("A"); g.pooled = U("pooled");
+    g.argmax = U("argmax"); g.perm = U("perm"); g.safe = U("safe"); g.st = U("st"); g.dist_fx = U("dist_fx");
+    g.active = U("active"); g.prev_active = U("prev_active"); g.out = U("out");
+    g.ctrl_w = U("ctrl_w"); g.ctrl_v = U("ctrl_v"); g.cbf_w = U("cbf_w"); g.cbf_rm = U("cbf_rm"); g.cbf_v = U("cbf_v");
+    g.delta = U("delta"); g.h = U("h"); g.rptr = U("rptr"); g.redges = U("redges"); g.csr_ws = U("csr_ws");
+    g.dEv = U("dEv"); g.ctl = U("ctl"); g.ew = U("ew"); g.scan_ws = U("scan_ws"); g.scan_ws_env = I("scan_ws_env");
+    const py::tuple lc = c["loss_consts"].cast<py::tuple>();
+    if (lc.size() < 7) throw std::invalid_argument("EpisodeDriver: loss_consts needs 7 values");
+    g.lc.eps_dang = lc[0].cast<float>(); g.lc.dt_alpha = lc[1].cast<float>(); g.lc.w_dang = lc[2].cast<float>();
+    g.lc.w_safe = lc[3].cast<float>(); g.lc.w_dang_d = lc[4].cast<float>(); g.lc.w_safe_d = lc[5].cast<float>();
+    g.lc.scale = lc[6].cast<float>();
+    g.stream = U("stream");
+    if (g.B < 1 || g.N < 1 || g.Nn < g.N || g.K < 1 || g.K > 16 || g.K > g.Nn || (g.D != 2 && g.D != 3) ||
+        g.max_steps < 0 || g.loops < 0 || g.prec_ctrl < 0 || g.prec_ctrl > 2 || g.prec_cbf < 0 || g.prec_cbf > 2)
+      throw std::invalid_argument("EpisodeDriver: bad dimensions");
+    if (g.check_every < 1) g.check_every = 1;
+    if (!g.S0 || !g.S1 || g.S0 == g.S1 || !g.G || !g.idx || !g.A || !g.argmax || !g.perm || !g.safe || !g.st ||
+        !g.dist_fx || !g.active || !g.prev_active || !g.out || !g.ctrl_w || !g.ctrl_v || (g.prec_ctrl == 2 && !g.pooled))
+      throw std::invalid_argument("EpisodeDriver: a required buffer is missing");
+    if (g.refine && g.loops > 0) {
+      if (g.prec_cbf == 1) throw std::invalid_argument("EpisodeDriver: the safety filter has no fp16 build");
+      if (!g.cbf_w || !g.cbf_rm || !g.cbf_v || !g.delta || !g.h || !g.rptr || !g.redges || g.cbf_blocks < 1)
+        throw std::invalid_argument("EpisodeDriver: a filter buffer is missing");
+      if (g.persistent ? (!g.ew || g.Nn > 64) : (!g.dEv || !g.ctl || g.refine_blocks < 1))
+        throw std::invalid_argument("EpisodeDriver: the filter's result words / workspace are missing");
+    }
+    return g;
+  }
+
+  std::pair<int, int> loop(const Cfg& g) {
+    hipStream_t st = ST(g.stream);
+    const bool filter = g.refine && g.loops > 0;
+    u64 S[2] = {g.S0, g.S1};
+    int cur = 0, t = 0;
+    mb::EpisodeArgs e{};
+    e.s_env = g.Nn; e.dim = g.D; e.B = g.B; e.N = g.N;
+    e.A = P<const float>(g.A); e.delta = filter ? P<float>(g.delta) : nullptr; e.G = P<const float>(g.G);
+    e.dt = g.dt;
+    e.st = P<long long>(g.st); e.dist_fx = P<unsigned long long>(g.dist_fx); e.safe = P<float>(g.safe);
+    e.active = P<uint8_t>(g.active); e.prev_active = P<uint8_t>(g.prev_active);
+    e.ctl = P<const unsigned long long>(g.ctl); e.ew = P<unsigned long long>(g.ew);
+    e.loops = g.loops; e.mode = !filter ? 0 : g.persistent ? 2 : 1;
+    e.thr_fx = (unsigned long long)std::llrint((double)g.done_thr * (double)g.N * mb::FX_DIST);
+    e.thr = g.done_thr;
+    e.out = P<long long>(g.out);
+    for (; t < g.max_steps;) {
+      scan(g, S[cur], true, st);
+      ctrl(g, S[cur], st);
+      if (filter) refine(g, S[cur], st);
+      e.S_cur = P<const float4>(S[cur]); e.S_next = P<float4>(S[cur ^ 1]);
+      chk(mb_episode_advance(&e, st), "episode_advance");
+      chk(mb_episode_tally(&e, st), "episode_tally");
+      cur ^= 1;
+      ++t;
+      if (t % g.check_every == 0 && t < g.max_steps) {
+        chk(hipMemcpyAsync(alive_host_, P<const long long>(g.st) + mb::EP_ALIVE, sizeof(long long),
+                           hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        chk(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (*alive_host_ == 0) break;
+      }
+    }
+    scan(g, S[cur], false, st);           // the safety count of the final state
+    e.S_cur = P<const float4>(S[cur]); e.S_next = nullptr;
+    chk(mb_episode_final(&e, st), "episode_final");
+    return {t, cur};
+  }
+
+  void scan(const Cfg& g, u64 S, bool knn, hipStream_t st) {
+    const int R = g.D == 2 ? 1 : 2;
+    mb::CellSortArgs c{};
+    c.S = P<const float4>(S); c.s_env = g.Nn; c.B = g.B; c.N = g.Nn; c.L = g.L; c.perm = P<int>(g.perm); c.rec = R;
+    chk(mb_cell_sort(&c, st), "cell_sort");
+    mb::ScanArgs a{};
+    a.S = P<const float4>(S); a.s_env = g.Nn; a.perm = P<const int>(g.perm);
+    a.B = g.B; a.N = g.N; a.K = knn ? g.K : 1; a.Nn = g.Nn; a.dim = g.D;
+    a.idx = knn ? P<int>(g.idx) : nullptr; a.i_env = knn ? (long)g.N * g.K : 0;
+    a.safe = P<float>(g.safe); a.sf_env = 1;
+    a.r2_train = g.r2_train; a.ttc_train = g.ttc_train; a.r2_check = g.r2_check; a.ttc_check = g.ttc_check;
+    a.do_knn = knn ? 1 : 0; a.do_safety = 1;
+    a.ws = P<float4>(g.scan_ws); a.ws_env = g.scan_ws_env;
+    chk(mb_scan(&a, st), "scan");
+  }
+
+  void ctrl(const Cfg& g, u64 S, hipStream_t st) {
+    const int prow = g.prec_ctrl == 2 ? 256 : 128;
+    mb::CtrlArgs a{};
+    a.dim = g.D; a.apw = g.apw;
+    a.S = P<const float4>(S); a.s_env = g.Nn; a.G = P<const float>(g.G);
+    a.idx = P<const int>(g.idx); a.i_env = (long)g.N * g.K;
+    a.B = g.B; a.N = g.N; a.K = g.K;
+    a.wpack = P<const h16>(g.ctrl_w); a.f_edge = g.f_edge; a.f_node = g.f_node; a.wvec = P<const float>(g.ctrl_v);
+    a.A = P<float>(g.A); a.a_env = g.N;
+    a.dt = g.dt; a.obs_r = g.obs_r; a.sqrt3 = g.sqrt3;
+    a.pooled = P<h16>(g.pooled); a.p_env = (long)g.N * prow;
+    a.argmax = P<uint8_t>(g.argmax); a.am_env = (long)g.N * 128;
+    chk((g.prec_ctrl == 2 ? mb_ctrl_fwd_x3 : g.prec_ctrl == 1 ? mb_ctrl_fwd_f16 : mb_ctrl_fwd)(&a, g.num_cu, st), "ctrl_fwd");
+  }
+
+  void refine(const Cfg& g, u64 S, hipStream_t st) {
+    mb::CbfFwdArgs a{};
+    a.dim = g.D;
+    a.S = P<const float4>(S); a.s_env = g.Nn; a.s_step = (long)g.B * g.Nn; a.idx = P<const int>(g.idx);
+    a.B = g.B; a.T = 1; a.N = g.N; a.K = g.K; a.two = 0;
+    a.wpack = P<const h16>(g.cbf_w); a.f_fwd = g.f_cbf; a.wvec = P<const float>(g.cbf_v);
+    a.h_out = P<float>(g.h);
+    a.lc = g.lc;
+    a.obs_r = g.obs_r; a.dist_thr = g.dist_thr; a.dist_eps = g.dist_eps;
+    chk((g.prec_cbf == 2 ? mb_cbf_fwd_x3 : mb_cbf_fwd)(&a, g.cbf_blocks, st), "cbf_fwd");
+    mb::CsrArgs r{};
+    r.idx = P<const int>(g.idx); r.G = g.B; r.N = g.N; r.K = g.K; r.Nn = g.Nn;
+    r.ptr = P<int>(g.rptr); r.edges = P<int>(g.redges); r.ws = P<int>(g.csr_ws);
+    chk(mb_rev_csr(&r, st), "rev_csr");
+    const u64 mask = g.mask_done ? g.active : 0;     // validate.py's rule: a finished env is not refined
+    if (g.persistent)
+      chk(refine_small(S, g.Nn, g.D, g.idx, g.A, g.delta, g.h, g.B, g.N, g.Nn, g.K, g.cbf_w, g.f_cbf, g.cbf_rm, g.cbf_v,
+                       g.rptr, g.redges, g.ew, g.loops, g.dt, g.dt_alpha, g.lr, g.obs_r, g.dist_thr, g.dist_eps, 0, 0,
+                       mask, g.prec_cbf, g.stream), "refine_small");
+    else
+      chk(refine_loop(S, g.Nn, g.D, g.idx, g.A, g.delta, g.h, g.B, g.N, g.Nn, g.K, g.cbf_w, g.f_cbf, g.cbf_rm, g.cbf_v,
+                      g.dEv, g.rptr, g.redges, g.ctl, g.loops, g.dt, g.dt_alpha, g.lr, g.obs_r, g.dist_thr, g.dist_eps,
+                      0, 0, mask, g.refine_blocks, g.prec_cbf, g.stream), "refine_loop");
+  }
+
+  long long* alive_host_ = nullptr;
+};
+
+// The three launches of csrc/episode.hip on their own (which: 0 advance, 1 tally, 2 final), with the
+// arguments EpisodeDriver hands them per step; validated in ops/native.py.
+int episode_kernel(int which, u64 S_cur, u64 S_next, long s_env, int dim, int B, int N, u64 A, u64 delta, u64 G,
+                   float dt, u64 st, u64 dist_fx, u64 safe, u64 active, u64 prev_active, u64 ctl, u64 ew, int loops,
+                   int mode, float thr, u64 out, u64 stream) {
+  mb::EpisodeArgs e{};
+  e.S_cur = P<const float4>(S_cur); e.S_next = P<float4>(S_next); e.s_env = s_env; e.dim = dim; e.B = B; e.N = N;
+  e.A = P<const float>(A); e.delta = P<float>(delta); e.G = P<const float>(G); e.dt = dt;
+  e.st = P<long long>(st); e.dist_fx = P<unsigned long long>(dist_fx); e.safe = P<float>(safe);
+  e.active = P<uint8_t>(active); e.prev_active = P<uint8_t>(prev_active);
+  e.ctl = P<const unsigned long long>(ctl); e.ew = P<unsigned long long>(ew); e.loops = loops; e.mode = mode;
+  e.thr_fx = (unsigned long long)std::llrint((double)thr * (double)N * mb::FX_DIST);
+  e.thr = thr;
+  e.out = P<long long>(out);
+  return which == 0 ? mb_episode_advance(&e, ST(stream)) : which == 1 ? mb_episode_tally(&e, ST(stream))
+                                                                       : mb_episode_final(&e, ST(stream));
+}
+
 }  // namespace
 
 void register_runtime(py::module& m) {
   m.def("refine_loop", &refine_loop);
   m.def("refine_small", &refine_small);
+  m.def("episode_kernel", &episode_kernel);
+  py::class_<EpisodeDriver>(m, "EpisodeDriver")
+      .def(py::init<>())
+      .def("run", &EpisodeDriver::run, py::arg("cfg"));
   py::class_<BpttDriver>(m, "BpttDriver")
       .def(py::init<py::dict>())
       .def("run", &BpttDriver::run, py::arg("T"), py::arg("act_coef"), py::arg("stream"), py::arg("use_acts") = false);

@@ -3,7 +3,8 @@
     python evaluate.py --num_agents 32 [--model_path ckpt.pt] [--num_envs 4] [--episodes 10]
                        [--max_steps 50] [--no_refine] [--refine_space actions|gains] [--diagnose]
                        [--dim 2|3] [--num_obstacles M] [--dtype fp32|bf16|fp16]
-                       [--refine_impl autograd|native] [--device auto|cpu|hip] [--gpu 0]
+                       [--refine_impl autograd|native] [--rollout_impl python|native]
+                       [--device auto|cpu|hip] [--gpu 0]
 
 Prints one JSON line: safety rate, reaching rate, mean final goal distance, refinement
 iterations. Without --model_path the networks are random-initialised (plumbing check).
@@ -11,7 +12,9 @@ iterations. Without --model_path the networks are random-initialised (plumbing c
 class can express); --diagnose adds the share of unsafe pairs that are top-K neighbours.
 --dim / --num_obstacles select the scene family (a checkpoint's dimension is read from its CBF
 input layer and must agree with --dim); --dtype is the MFMA operand precision on a HIP device;
---refine_impl native runs the refinement as the device-resident safety filter (HIP only).
+--refine_impl native runs the refinement as the device-resident safety filter (HIP only);
+--rollout_impl native runs each batch of episodes as one native call (HIP only; with --no_refine
+or --refine_impl native, not with --diagnose or --refine_space gains).
 """
 from __future__ import annotations
 
@@ -39,6 +42,7 @@ def main(argv=None):
     ap.add_argument("--num_obstacles", type=int, default=0)
     ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32")
     ap.add_argument("--refine_impl", choices=["autograd", "native"], default="autograd")
+    ap.add_argument("--rollout_impl", choices=["python", "native"], default="python")
     args = ap.parse_args(argv)
     if args.gpu is not None:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)
@@ -64,7 +68,8 @@ def main(argv=None):
         ckpt.load_models(args.model_path, ctrl, cbf)
     cfg = EvalConfig(num_agents=args.num_agents, num_envs=args.num_envs, seed=args.seed, refine=not args.no_refine,
                      refine_space=args.refine_space, diagnose=args.diagnose, dim=args.dim,
-                     num_obstacles=args.num_obstacles, dtype=args.dtype, refine_impl=args.refine_impl)
+                     num_obstacles=args.num_obstacles, dtype=args.dtype, refine_impl=args.refine_impl,
+                     rollout_impl=args.rollout_impl)
     if args.episodes is not None:
         cfg.episodes = args.episodes
     if args.max_steps is not None:
@@ -73,10 +78,17 @@ def main(argv=None):
         cfg.refine_loops = args.refine_loops
     if args.refine_lr is not None:
         cfg.refine_lr = args.refine_lr
-    out = evaluate(ctrl, cbf, cfg, device=dev)
+    try:
+        out = evaluate(ctrl, cbf, cfg, device=dev)
+    except ValueError as e:
+        if cfg.rollout_impl != "native" or "rollout_impl" not in str(e):
+            raise
+        ap.error(str(e))
     out.update({"num_agents": args.num_agents, "num_envs": args.num_envs, "episodes": cfg.episodes,
                 "refine": cfg.refine, "device": str(dev), "dim": cfg.dim, "num_obstacles": cfg.num_obstacles,
                 "refine_impl": cfg.refine_impl, "dtype": cfg.dtype})
+    if cfg.rollout_impl != "python":
+        out["rollout_impl"] = cfg.rollout_impl
     print(json.dumps(out), flush=True)
     return out
 

@@ -103,6 +103,8 @@ class TrainConfig:
     val_envs: int = 4                 # held-out scenes per rank, fixed for the whole run
     val_refine: bool = True           # also run the rollout with the CBF safety filter
     val_refine_loops: int = REFINE_LOOPS
+    val_impl: str = "python"          # "python": the rollout as torch ops | "native" (HIP only, opt-in): one
+                                      # native call per rollout (ops/episode.py), the same integer totals
     save_best: bool = False           # keep <model_path>.best (+ .best.json) at the best validation so far
     best_metric: str = ""             # a val_*_rate key, higher is better; "": val_refined_safety_rate
                                       # (val_safety_rate with val_refine off)

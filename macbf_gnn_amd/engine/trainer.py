@@ -89,7 +89,7 @@ class Trainer:
         self._best_read = False
         if cfg.val_every or cfg.save_best:
             from .. import validate as V
-            V.check_config(cfg)
+            V.check_config(cfg, self.device)
         # the next iteration's scenarios on a side stream, launched as soon as enqueued: it runs in
         # the idle issue slots of the current iteration's CBF backward (inline sampling and a side
         # stream gated on the enqueued work both measured slower, docs/PERF.md round 5)

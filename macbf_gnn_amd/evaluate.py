@@ -55,6 +55,9 @@ class EvalConfig:
     dtype: str = "fp32"         # MFMA operand precision on HIP: evaluate() sets the networks' mfma_dtype
                                 # (fp32 | bf16 | fp16); no effect on CPU (fp32 oracle)
     refine_impl: str = "autograd"   # "autograd" or "native" (HIP only): the device-resident filter
+    rollout_impl: str = "python"    # "python" or "native" (HIP only, opt-in): the whole batch of episodes as one
+                                    # native call (ops/episode.py); needs refine off or refine_impl="native",
+                                    # refine_space="actions", diagnose off and early_stop on
 
 
 MFMA_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
@@ -165,11 +168,56 @@ def _unsafe_diag(s_next, idx, obstacles=None):
     return unsafe.sum(), seen.sum()
 
 
+def check_rollout_impl(cfg: EvalConfig, device) -> None:
+    """``rollout_impl="native"`` runs the episodes of ``rollout_eval`` as one native call: every option
+    it cannot honour is an error that names the option, never a silent change of what is measured."""
+    if cfg.rollout_impl not in ("python", "native"):
+        raise ValueError(f"unknown rollout_impl {cfg.rollout_impl!r} (python or native)")
+    if cfg.rollout_impl != "native":
+        return
+    if cfg.diagnose:
+        raise ValueError("rollout_impl='native' has no diagnose mode: use diagnose=False or rollout_impl='python'")
+    if cfg.refine and cfg.refine_space != "actions":
+        raise ValueError(f"rollout_impl='native' refines actions only: refine_space={cfg.refine_space!r} needs "
+                         "rollout_impl='python'")
+    if cfg.refine and cfg.refine_impl != "native":
+        raise ValueError(f"rollout_impl='native' runs the device-resident filter: refine_impl={cfg.refine_impl!r} "
+                         "needs rollout_impl='python' (or set refine_impl='native' or refine=False)")
+    if not cfg.early_stop:
+        raise ValueError("rollout_impl='native' stops moving a finished scene: early_stop=False needs "
+                         "rollout_impl='python'")
+    if torch.device(device).type != "cuda":
+        raise ValueError("rollout_impl='native' runs the episodes as native HIP kernels (ops/episode.py): it needs a "
+                         "HIP device; use rollout_impl='python' on CPU")
+
+
+def _rollout_native(controller, cbf, s0, g, cfg: EvalConfig, obstacles) -> Dict[str, float]:
+    """``rollout_eval``'s result dict from the count vector of ``ops.episode.run_episodes`` with the
+    evaluation's rule (``mask_done=False``: a finished env is still refined until the batch stops)."""
+    from . import validate as V
+    from .ops import episode
+    B, N, _ = s0.shape
+    vec = episode.run_episodes(controller, cbf, s0, g, obstacles, refine=cfg.refine, loops=cfg.refine_loops,
+                               lr=cfg.refine_lr, max_steps=cfg.max_steps, top_k=cfg.top_k, mask_done=False,
+                               check_every=V.CHECK_EVERY)
+    c = dict(zip(V.COUNTS, (int(x) for x in vec.tolist())))          # the one host read
+    # the Python loop's fp32 mean over a (B, N) 0 / 1 tensor, formed the same way from the count
+    hit = torch.arange(B * N, device=s0.device).view(B, N) < c["reached_agents"]
+    return {"safety_rate": float(c["safe_agent_steps"]) / max(c["agent_steps"], 1),
+            "reaching_rate": float(hit.float().mean()),
+            "mean_goal_dist": c["goal_dist_fx"] / V.DIST_FX / max(c["agents"], 1),
+            "steps": c["steps"], "agent_steps": c["agent_steps"],
+            "refine_iters": c["refine_iters"]}
+
+
 def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dict[str, float]:
     """One batch of episodes from ``s0`` (B, N, 2D) towards ``g`` (B, N, D); ``obstacles`` (B, M, D)
     are static graph nodes seen by kNN, the controller, the CBF and the safety check."""
     if cfg.refine_impl not in ("autograd", "native"):
         raise ValueError(f"unknown refine_impl {cfg.refine_impl!r} (autograd or native)")
+    check_rollout_impl(cfg, s0.device)
+    if cfg.rollout_impl == "native":
+        return _rollout_native(controller, cbf, s0, g, cfg, obstacles)
     native_filter = cfg.refine and cfg.refine_impl == "native" and cfg.refine_space != "gains"
     if cfg.refine_impl == "native" and not s0.is_cuda:
         raise ValueError("refine_impl='native' is the HIP safety filter (csrc/refine.hip): it needs a HIP device; "
@@ -258,6 +306,7 @@ def evaluate(controller, cbf, cfg: EvalConfig, device: Optional[torch.device] = 
             raise ValueError(f"{name} was built for {net.in_dim // 2}-D states, the evaluation runs dim={cfg.dim}")
     if cfg.dtype not in MFMA_DTYPES:
         raise ValueError(f"dtype must be one of {sorted(MFMA_DTYPES)}, got {cfg.dtype!r}")
+    check_rollout_impl(cfg, device)
     if device.type == "cuda":
         controller.mfma_dtype = cbf.mfma_dtype = MFMA_DTYPES[cfg.dtype]
     controller.eval()

@@ -1375,3 +1375,230 @@ def stats_pack(sums, counts, local, row):
     if row.dtype != torch.float32 or row.numel() < 18 or not row.is_contiguous():
         raise NativeError("row must be a contiguous float32 row of >= 18")
     _ok(lib().stats_pack(ptr(sums), ptr(counts), ptr(local), ptr(row), stream_handle()), "stats_pack")
+
+
+# ----------------------------------------------------------------------------- closed-loop episodes
+EP_WORDS = 5                  # csrc/args.h: [alive, safe agent-steps, env steps, steps, filter iterations]
+EP_OUT = 8                    # result words, the order of validate.COUNTS
+EP_MODES = {None: 0, "loop": 1, "persistent": 2}
+_EPISODE_DRIVER = None
+
+
+def _ep(t, dtype, shape, name, required=True):
+    """Dtype, shape and contiguity of one tensor; the device is checked for all of a call's tensors
+    together, last (``_ep_device``), so every other mistake is reported without one."""
+    if t is None:
+        if required:
+            raise NativeError(f"{name} is required")
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise NativeError(f"{name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+    if tuple(t.shape) != tuple(shape):
+        raise NativeError(f"{name} shape {tuple(t.shape)} != {tuple(shape)}")
+    if not t.is_contiguous():
+        raise NativeError(f"{name} must be contiguous")
+
+
+def _ep_device(**tensors):
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise NativeError(f"{name} must be on the HIP device")
+
+
+def _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active):
+    """The checks shared by the three episode launches -> (B, N, Nn, D)."""
+    if S_cur is None or not isinstance(S_cur, torch.Tensor) or S_cur.dim() != 3:
+        raise NativeError("S_cur must be (B, Nn, 4|8) node records")
+    B, Nn, W = S_cur.shape
+    D = dim_of(S_cur)
+    if G is None or not isinstance(G, torch.Tensor) or G.dim() != 3 or G.shape[0] != B:
+        raise NativeError(f"G must be float32 (B={B}, N, D)")
+    N = G.shape[1]
+    if N < 1 or N > Nn:
+        raise NativeError(f"G has N = {N} agents but the records hold {Nn} nodes")
+    if B * N >= 2 ** 31 - 65536:
+        raise NativeError("too many agents for 32-bit indexing")
+    _ep(S_cur, torch.float32, (B, Nn, W), "S_cur")
+    _ep(G, torch.float32, (B, N, D), "G")
+    _ep(st, torch.int64, (EP_WORDS,), "st")
+    _ep(dist_fx, torch.int64, (B,), "dist_fx")
+    _ep(safe, torch.float32, (B,), "safe")
+    _ep(active, torch.uint8, (B,), "active")
+    _ep(prev_active, torch.uint8, (B,), "prev_active")
+    return B, N, Nn, D
+
+
+def _episode_launch(which, S_cur, S_next, N, D, A, delta, G, st, dist_fx, safe, active, prev_active, ctl, ew, loops, mode,
+                    out, what):
+    B, Nn = S_cur.shape[:2]
+    _ok(lib().episode_kernel(which, ptr(S_cur), ptr(S_next), Nn, D, B, N, ptr(A), ptr(delta), ptr(G), float(C.TIME_STEP),
+                             ptr(st), ptr(dist_fx), ptr(safe), ptr(active), ptr(prev_active), ptr(ctl), ptr(ew),
+                             int(loops), int(mode), float(C.DIST_MIN_CHECK), ptr(out), stream_handle()), what)
+
+
+def episode_advance(S_cur, S_next, A, delta, G, st, dist_fx, safe, active, prev_active):
+    """One Euler step of every agent (csrc/episode.hip episode_advance_kernel): S_next's agent records
+    = s + [v, A + delta] * dt of S_cur's (unchanged when st[0], the "some env still runs" word, is 0),
+    dist_fx[b] += sum_i |p'_i - g_i| * FX_DIST. S_cur / S_next (B, Nn, 4|8) distinct record buffers
+    (obstacle rows are not touched); A (B, N, D); delta (B, N, D) or None, zeroed once it is read."""
+    B, N, Nn, D = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
+    _ep(S_next, torch.float32, tuple(S_cur.shape), "S_next")
+    _ep(A, torch.float32, (B, N, D), "A")
+    _ep(delta, torch.float32, (B, N, D), "delta", required=False)
+    if S_next.data_ptr() == S_cur.data_ptr():
+        raise NativeError("S_next must not be S_cur")
+    _ep_device(S_cur=S_cur, S_next=S_next, A=A, delta=delta, G=G, st=st, dist_fx=dist_fx, safe=safe, active=active,
+               prev_active=prev_active)
+    _episode_launch(0, S_cur, S_next, N, D, A, delta, G, st, dist_fx, safe, active, prev_active, None, None, 0, 0, None,
+                    "episode_advance")
+
+
+def _episode_words(B, ctl, ew, loops):
+    loops = int(loops)
+    if loops < 0:
+        raise NativeError("loops must be >= 0")
+    if ctl is not None and ew is not None:
+        raise NativeError("ctl (loop filter) and ew (persistent filter) exclude each other")
+    if ctl is not None:
+        if not isinstance(ctl, torch.Tensor) or ctl.dim() != 1 or ctl.numel() < 2 * loops:
+            raise NativeError(f"ctl must be int64 with at least 2*loops = {2 * loops} words")
+        _ep(ctl, torch.int64, tuple(ctl.shape), "ctl")
+        return loops, 1
+    if ew is not None:
+        _ep(ew, torch.int64, (B, loops, 2), "ew")
+        return loops, 2
+    return loops, 0
+
+
+def episode_tally(S_cur, G, st, dist_fx, safe, active, prev_active, *, ctl=None, ew=None, loops=0):
+    """The step's bookkeeping (episode_tally_kernel, one workgroup), run after episode_advance:
+    st += [safe agents of S_cur of the envs that ran the step before, envs running, alive, the
+    filter's iterations], prev_active <- active, active &= dist_fx >= DIST_MIN_CHECK * N, st[0] =
+    any(active); dist_fx, safe (and ew) are cleared. ctl: the loop filter's control words; ew
+    (B, loops, 2): the persistent filter's; neither: no filter."""
+    B, N, Nn, D = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
+    loops, mode = _episode_words(B, ctl, ew, loops)
+    _ep_device(S_cur=S_cur, G=G, st=st, dist_fx=dist_fx, safe=safe, active=active, prev_active=prev_active, ctl=ctl, ew=ew)
+    _episode_launch(1, S_cur, None, N, D, None, None, G, st, dist_fx, safe, active, prev_active, ctl, ew, loops, mode, None,
+                    "episode_tally")
+
+
+def episode_final(S_cur, G, st, dist_fx, safe, active, prev_active, out):
+    """The result vector (episode_final_kernel), after the safety-only scan of the final state S_cur:
+    out (EP_OUT,) int64 in the order of validate.COUNTS."""
+    B, N, Nn, D = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
+    _ep(out, torch.int64, (EP_OUT,), "out")
+    _ep_device(S_cur=S_cur, G=G, st=st, dist_fx=dist_fx, safe=safe, active=active, prev_active=prev_active, out=out)
+    _episode_launch(2, S_cur, None, N, D, None, None, G, st, dist_fx, safe, active, prev_active, None, None, 0, 0, out,
+                    "episode_final")
+
+
+def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask_done, persistent, ctrl, cbf):
+    """A whole batch of closed-loop episodes as one native call (csrc/runtime.cpp EpisodeDriver).
+
+    buf: the call's device buffers (ops/episode.py allocates them): S0 / S1 (B, Nn, 4|8) record
+    buffers, both holding s_0 and the obstacle rows; G (B, N, D); idx (B, N, K) int32; A (B, N, D);
+    pooled (B, N, 128|256) 16-bit, argmax (B, N, 128) uint8; perm (B, Nn) int32; st (EP_WORDS,) int64 =
+    [1, 0, 0, 0, 0]; dist_fx (B,) int64 zero; safe (B,) float32 zero; active (B,) uint8 ones;
+    prev_active (B,) uint8 zero; out (EP_OUT,) int64; with refine and loops > 0 also delta (B, N, D)
+    zero, h (B, N, K), rptr (B, Nn+1) / redges (B, N*K) int32 and ctl (2*loops,) int64 + dEv
+    (B, N, K, D) (loop filter) or ew (B, loops, 2) int64 zero (persistent). ctrl / cbf: (wpack, wvec,
+    wrm, ModulePack) of the packed networks (cbf may be None without refine).
+    Returns (steps issued, index of the record buffer that holds the final state)."""
+    K, max_steps, check_every, loops = int(K), int(max_steps), int(check_every), int(loops)
+    if K < 1 or K > C.MAX_TOP_K:
+        raise NativeError(f"K = {K} outside 1..{C.MAX_TOP_K}")
+    if max_steps < 0 or check_every < 1 or loops < 0:
+        raise NativeError("max_steps >= 0, check_every >= 1 and loops >= 0 are required")
+    # what needs no device first: K, the loop counts, the filter's precision
+    qc = 0
+    bw = bv = brm = bmp = None
+    if refine:
+        if cbf is None:
+            raise NativeError("refine needs the packed CBF")
+        bw, bv, brm, bmp = cbf
+        qc = _half(bw, "CBF wpack", bmp.prec)
+        if qc == 1:
+            raise NativeError("safety filter: fp16 is not supported (the -1 upstream gradient has no loss scaling); "
+                              "use fp32 or bf16")
+    S0 = buf.get("S0")
+    B, N, Nn, D = _episode_state(S0, buf.get("G"), buf.get("st"), buf.get("dist_fx"), buf.get("safe"),
+                                 buf.get("active"), buf.get("prev_active"))
+    W = rec_width(D)
+    if K > Nn:
+        raise NativeError(f"bad K={K} for Nn={Nn}")
+    if Nn > SCAN_MAX_NODES:
+        raise NativeError(f"at most {SCAN_MAX_NODES} graph nodes per env (got {Nn})")
+    _ep(buf.get("S1"), torch.float32, (B, Nn, W), "S1")
+    if buf["S1"].data_ptr() == S0.data_ptr():
+        raise NativeError("S1 must not be S0")
+    _ep(buf.get("idx"), torch.int32, (B, N, K), "idx")
+    _ep(buf.get("A"), torch.float32, (B, N, D), "A")
+    _ep(buf.get("perm"), torch.int32, (B, Nn), "perm")
+    _ep(buf.get("out"), torch.int64, (EP_OUT,), "out")
+    cw, cv, _, cmp_ = ctrl
+    pc = _half(cw, "controller wpack", cmp_.prec)
+    _ep(cw, cw.dtype, tuple(cw.shape), "controller wpack")
+    _ep(cv, torch.float32, tuple(cv.shape) if isinstance(cv, torch.Tensor) else (), "controller wvec")
+    if cv.numel() < 352 or cw.numel() < (cmp_.off["nw1f"] + 54) * 512 * _planes(pc):
+        raise NativeError("packed controller weights too small")
+    _ep(buf.get("pooled"), cw.dtype, (B, N, _prow(pc)), "pooled")
+    _ep(buf.get("argmax"), torch.uint8, (B, N, 128), "argmax")
+    filt = bool(refine) and loops > 0
+    if filt:
+        _ep(bw, bw.dtype, tuple(bw.shape), "CBF wpack")
+        _ep(bv, torch.float32, tuple(bv.shape) if isinstance(bv, torch.Tensor) else (), "CBF wvec")
+        if bv.numel() < 260 or bw.numel() < (bmp.off["w1f"] + 70) * 512 * _planes(qc):
+            raise NativeError("packed CBF weights too small")
+        _ep(brm, bw.dtype, (_planes(qc) * (128 * 68 + 64 * 148),), "CBF wrm")
+        _ep(buf.get("delta"), torch.float32, (B, N, D), "delta")
+        _ep(buf.get("h"), torch.float32, (B, N, K), "h")
+        _ep(buf.get("rptr"), torch.int32, (B, Nn + 1), "rptr")
+        _ep(buf.get("redges"), torch.int32, (B, N * K), "redges")
+        if B * N * K >= 2 ** 31 - 2 ** 21:
+            raise NativeError("too many edges for 32-bit indexing")
+        if persistent:
+            if not refine_small_eligible(Nn, K):
+                raise NativeError(f"the persistent filter takes envs of at most {SMALL_MAXN} graph nodes")
+            _ep(buf.get("ew"), torch.int64, (B, loops, 2), "ew")
+        else:
+            _ep(buf.get("ctl"), torch.int64, (2 * loops,), "ctl")
+            _ep(buf.get("dEv"), torch.float32, (B, N, K, D), "dEv")
+    _ep_device(**{k: t for k, t in buf.items() if isinstance(t, torch.Tensor)}, ctrl_wpack=cw, ctrl_wvec=cv,
+               cbf_wpack=bw, cbf_wvec=bv, cbf_wrm=brm)
+    dev = S0.device
+    ws, ws_f4 = scan_ws(B, Nn, dev)
+    csr_ws = None
+    if filt and (2 * Nn + 1) * 4 > 150 * 1024:
+        csr_ws = _workspace("csr", B * Nn * 4, dev)
+    E = B * N * K
+    global _EPISODE_DRIVER
+    if _EPISODE_DRIVER is None:
+        _EPISODE_DRIVER = lib().EpisodeDriver()
+    cfg = dict(B=B, N=N, Nn=Nn, K=K, D=D, num_cu=num_cu(dev), prec_ctrl=pc, prec_cbf=qc,
+               apw=ctrl_fwd_apw(B * N, dev, N), max_steps=max_steps, check_every=check_every,
+               refine=int(filt), persistent=int(bool(persistent)), loops=loops, mask_done=int(bool(mask_done)),
+               cbf_blocks=cbf_fwd_grid(E, dev) if filt else 0, refine_blocks=refine_grid(E, dev, qc) if filt else 0,
+               f_edge=int(cmp_.off["ew1f"]), f_node=int(cmp_.off["nw1f"]), f_cbf=int(bmp.off["w1f"]) if filt else 0,
+               L=float(max(1.0, N / C.AGENT_DENSITY) ** (1.0 / D)),
+               r2_train=float(C.DIST_MIN_THRES * C.DIST_MIN_THRES), ttc_train=float(C.TIME_TO_COLLISION),
+               r2_check=float(C.DIST_MIN_CHECK * C.DIST_MIN_CHECK), ttc_check=float(C.TIME_TO_COLLISION_CHECK),
+               dt=float(C.TIME_STEP), dt_alpha=float(C.TIME_STEP * C.ALPHA_CBF), lr=float(lr), obs_r=float(C.OBS_RADIUS),
+               sqrt3=float(C.SQRT3), dist_thr=float(C.DIST_MIN_THRES), dist_eps=float(C.CBF_DIST_EPS_COORD * D),
+               done_thr=float(C.DIST_MIN_CHECK), loss_consts=LOSS_CONSTS,
+               S0=ptr(S0), S1=ptr(buf["S1"]), G=ptr(buf["G"]), idx=ptr(buf["idx"]), A=ptr(buf["A"]),
+               pooled=ptr(buf["pooled"]), argmax=ptr(buf["argmax"]), perm=ptr(buf["perm"]), safe=ptr(buf["safe"]),
+               st=ptr(buf["st"]), dist_fx=ptr(buf["dist_fx"]), active=ptr(buf["active"]),
+               prev_active=ptr(buf["prev_active"]), out=ptr(buf["out"]),
+               ctrl_w=ptr(cw), ctrl_v=ptr(cv), cbf_w=ptr(bw) if filt else 0, cbf_rm=ptr(brm) if filt else 0,
+               cbf_v=ptr(bv) if filt else 0, delta=ptr(buf.get("delta")) if filt else 0, h=ptr(buf.get("h")) if filt else 0,
+               rptr=ptr(buf.get("rptr")) if filt else 0, redges=ptr(buf.get("redges")) if filt else 0, csr_ws=ptr(csr_ws),
+               dEv=ptr(buf.get("dEv")) if filt and not persistent else 0,
+               ctl=ptr(buf.get("ctl")) if filt and not persistent else 0,
+               ew=ptr(buf.get("ew")) if filt and persistent else 0,
+               scan_ws=ptr(ws), scan_ws_env=int(ws_f4), stream=stream_handle())
+    try:
+        steps, cur = _EPISODE_DRIVER.run(cfg)
+    except (RuntimeError, ValueError) as e:
+        raise NativeError(f"episode driver: {e}") from e
+    return int(steps), int(cur)

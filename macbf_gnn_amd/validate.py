@@ -20,6 +20,11 @@ Everything is counted on the device in integers. The host looks at the "all done
 neither the counts nor the states, so the result does not depend on that period. The count vectors
 are summed over the DP ranks before any ratio is taken: every rank returns the same dict.
 
+``Validator(impl="native")`` (``TrainConfig.val_impl``, ``train.py --val_impl native``; HIP only,
+opt-in) runs each rollout as one native call, ``ops.episode.run_episodes(..., mask_done=True)``:
+the same count vector, so everything after ``rollout()`` is shared. ``"python"`` stays the default
+and the reference.
+
 Precision (HIP): the networks run at the training ``dtype``. The filter has no fp16 build (its -1
 upstream gradient has no loss scaling), so a run that trains in fp16 validates both networks in
 bf16. ``validate`` puts ``mfma_dtype`` and the train / eval mode of both modules back, draws from
@@ -48,8 +53,19 @@ def default_best_metric(cfg) -> str:
     return cfg.best_metric or ("val_refined_safety_rate" if cfg.val_refine else "val_safety_rate")
 
 
-def check_config(cfg):
-    """The validation entries of a TrainConfig that cannot work, reported before the run starts."""
+IMPLS = ("python", "native")
+
+
+def check_config(cfg, device=None):
+    """The validation entries of a TrainConfig that cannot work, reported before the run starts.
+    ``device``: the device the run resolved to (``cfg.device`` may be "auto")."""
+    impl = getattr(cfg, "val_impl", "python")
+    if impl not in IMPLS:
+        raise ValueError(f"val_impl must be one of {IMPLS}, got {impl!r}")
+    on_cpu = cfg.device == "cpu" or (device is not None and torch.device(device).type == "cpu")
+    if impl == "native" and on_cpu:
+        raise ValueError("val_impl='native' runs the validation rollouts as native HIP episodes (ops/episode.py): it "
+                         "needs a HIP device; use val_impl='python' on CPU")
     if cfg.val_every < 0 or cfg.val_envs < 1 or cfg.val_refine_loops < 0:
         raise ValueError("val_every must be >= 0, val_envs >= 1 and val_refine_loops >= 0")
     m = default_best_metric(cfg)
@@ -87,11 +103,16 @@ def metrics_from_counts(nom: Dict[str, int], ref: Optional[Dict[str, int]], num_
 
 
 class Validator:
-    def __init__(self, cfg: C.TrainConfig, device: torch.device, dp=None):
+    def __init__(self, cfg: C.TrainConfig, device: torch.device, dp=None, impl: Optional[str] = None):
         from .ops import scenario
         self.cfg = cfg
         self.device = device
         self.dp = dp
+        self.impl = impl or getattr(cfg, "val_impl", "python")     # "native": rollout() is one native call
+        if self.impl not in IMPLS:
+            raise ValueError(f"impl must be one of {IMPLS}, got {self.impl!r}")
+        if self.impl == "native" and torch.device(device).type != "cuda":
+            raise ValueError("impl='native' needs a HIP device; use impl='python' on CPU")
         rank = dp.rank if dp is not None else 0
         s0, g, obs = scenario.generate(cfg.val_envs, cfg.num_agents, seed=scenario._mix(cfg.seed, VAL_SALT),
                                        iteration=0, rank=rank, device=device, dim=cfg.dim,
@@ -122,6 +143,11 @@ class Validator:
         """One batch of episodes from the fixed scenes -> this rank's totals, an int64 device vector
         in the order of ``COUNTS``. No host read except the "all done" flag every CHECK_EVERY steps."""
         s, g, obs = self.s0, self.g, self.obs
+        if self.impl == "native":
+            from .ops import episode
+            return episode.run_episodes(controller, cbf, s, g, obs, refine=refine, loops=self.cfg.val_refine_loops,
+                                        lr=C.REFINE_LEARNING_RATE, max_steps=self.max_steps, top_k=self.cfg.top_k,
+                                        mask_done=True, check_every=CHECK_EVERY)
         B, N, _ = s.shape
         D = s.shape[-1] // 2
         k = min(self.cfg.top_k, N)

@@ -7,6 +7,8 @@
                                               [--refine_loops 50]
     python scripts/bench_validate.py impl     [--num_agents 32] [--val_envs 8] [--dtype bf16]
                                               [--model_path checkpoints/cfg2_6k.pt] [--rounds 5]
+    python scripts/bench_validate.py episode  [--num_agents 1024] [--val_envs 4] [--dtype fp32]
+                                              [--model_path checkpoints/headline_4k.pt] [--rounds 5]
 
 ``validate``: wall time of ``Validator.validate`` (both rollouts, the totals' read included), one
 warm-up call (scenes, packing tables) and ``--rounds`` timed ones.
@@ -23,6 +25,13 @@ one process: the filter alone on the recorded steps of one filtered episode (as 
 the recorded masks), and a whole ``validate()`` with ``MACBF_REFINE_SMALL`` forcing each path.
 Reports the minimum, the mean and the spread (max - min) over the rounds, and checks that both
 paths gave the same iteration count and the same validation counts.
+
+``episode``: the two implementations of the validation rollouts, ``Validator(impl="python")`` (the
+rollout as torch ops) and ``impl="native"`` (one native call per rollout, ops/episode.py), as whole
+``validate()`` calls on the same scenes, interleaved round by round in one process: one warm-up
+round, ``--rounds`` timed ones. Reports the minimum, the mean and the spread (max - min) of each, the
+difference of the minima, whether it exceeds the Python path's spread, and whether both gave the
+same counts.
 
 Prints one JSON line. Without ``--model_path`` the networks are random-initialised."""
 import argparse
@@ -67,7 +76,7 @@ def record_episode(v, ctrl, cbf, loops):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["validate", "mask", "impl"])
+    ap.add_argument("mode", choices=["validate", "mask", "impl", "episode"])
     ap.add_argument("--num_agents", type=int, default=1024)
     ap.add_argument("--val_envs", type=int, default=4)
     ap.add_argument("--dim", type=int, default=2)
@@ -95,6 +104,27 @@ def main():
         out.update({k: x for k, x in res.items() if k != "val_ms"})
         out.update({"val_ms": ms, "val_ms_min": min(ms), "val_ms_mean": sum(ms) / len(ms),
                     "counts": v.last_counts})
+    elif a.mode == "episode":
+        impls = ("python", "native")
+        val, counts = {n: [] for n in impls}, {}
+        for rnd in range(a.rounds + 1):                  # round 0 warms up
+            for name in impls:
+                v.impl = name
+                ms = v.validate(ctrl, cbf)["val_ms"]
+                if rnd:
+                    val[name].append(ms)
+                counts[name] = v.last_counts
+        for name in impls:
+            out[f"{name}_val_ms"] = val[name]
+            out[f"{name}_val_ms_min"] = min(val[name])
+            out[f"{name}_val_ms_mean"] = sum(val[name]) / len(val[name])
+            out[f"{name}_val_ms_spread"] = max(val[name]) - min(val[name])
+        gain = out["python_val_ms_min"] - out["native_val_ms_min"]
+        fx = lambda c: {r: {k: x for k, x in d.items() if k != "goal_dist_fx"} for r, d in c.items()}
+        out.update({"min_gain_ms": gain, "gain_exceeds_python_spread": gain > out["python_val_ms_spread"],
+                    "same_val_counts": fx(counts["python"]) == fx(counts["native"]),
+                    "goal_dist_fx": {n: {r: d["goal_dist_fx"] for r, d in counts[n].items()} for n in impls},
+                    "counts": counts["native"]})
     elif a.mode == "impl":
         impls = ("loop", "persistent")
         knob = {"loop": "0", "persistent": "1"}

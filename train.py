@@ -48,6 +48,8 @@ def parse_args(argv=None):
     p.add_argument("--val_envs", type=int, default=None, help="validation scenes per rank")
     p.add_argument("--no_val_refine", action="store_true", help="validate the controller only (no safety filter)")
     p.add_argument("--val_refine_loops", type=int, default=None)
+    p.add_argument("--val_impl", type=str, default="python", choices=["python", "native"],
+                   help="validation rollouts as torch ops (python) or as one native call each (native, HIP only)")
     p.add_argument("--save_best", action="store_true",
                    help="keep <model_path>.best at the best validation value of --best_metric")
     p.add_argument("--best_metric", type=str, default="",
@@ -63,7 +65,8 @@ def build_config(args):
                         alternate_every=args.alternate_every, early_stop=not args.no_early_stop,
                         model_path=args.model_path, log_path=args.log_path, dim=args.dim,
                         num_obstacles=args.num_obstacles, graph=args.graph, val_every=args.val_every,
-                        val_refine=not args.no_val_refine, save_best=args.save_best, best_metric=args.best_metric)
+                        val_refine=not args.no_val_refine, save_best=args.save_best, best_metric=args.best_metric,
+                        val_impl=args.val_impl)
     for name in ("train_steps", "inner_loops", "top_k", "lr", "display_steps", "save_steps", "val_envs",
                  "val_refine_loops"):
         v = getattr(args, name)
