@@ -1,31 +1,37 @@
 // pybind11 module macbf_gnn_amd._host: the CPU-side native runtime (no HIP dependency).
-// Arguments are host buffer addresses; shapes/dtypes are validated in macbf_gnn_amd/ops/host.py.
+// Arguments are host buffer addresses, passed by keyword and read through Args (csrc/pyargs.h);
+// shapes/dtypes are validated in macbf_gnn_amd/ops/host.py.
 #include <pybind11/pybind11.h>
 
+#include "../pyargs.h"
 #include "scenario_host.h"
 
-namespace py = pybind11;
-typedef unsigned long long u64;
-
-static int sample_scenarios(u64 S, u64 G, u64 obs, u64 status, int B, int N, int dim, int M, float L, float r,
-                            float spread, u64 seed, int max_rounds, int threads) {
-  mbh::ScenarioSpec sp{B, N, dim, M, L, r, spread, (uint64_t)seed, max_rounds};
-  py::gil_scoped_release nogil;
-  return mbh::sample_scenarios(sp, reinterpret_cast<const float*>(obs), reinterpret_cast<float*>(S),
-                               reinterpret_cast<float*>(G), reinterpret_cast<int*>(status), threads);
+// f, run without the GIL
+template <typename R, typename... A>
+static auto nogil(R (*f)(A...)) {
+  return [f](A... a) { py::gil_scoped_release g; return f(a...); };
 }
 
-static float min_pair_distance(u64 p, int n, int dim, int stride, float L, float cutoff) {
-  py::gil_scoped_release nogil;
-  return mbh::min_pair_distance(reinterpret_cast<const float*>(p), n, dim, stride, L, cutoff);
+static int sample_scenarios(py::kwargs kw) {
+  Args x("sample_scenarios", kw);
+  mbh::ScenarioSpec sp{};
+  x("B", sp.B); x("N", sp.N); x("dim", sp.dim); x("M", sp.M); x("L", sp.L); x("r", sp.r);
+  x("spread", sp.spread); sp.seed = x.u("seed"); x("max_rounds", sp.max_rounds);
+  return x.then(nogil(mbh::sample_scenarios), sp, x.ptr<const float>("obs"), x.ptr<float>("S"), x.ptr<float>("G"),
+                x.ptr<int>("status"), x.i("threads"));
 }
 
-static int sample_obstacles(u64 out, int B, int n_obs, int points, int dim, float L, u64 seed, u64 circle,
-                            u64 rect, u64 sphere) {
-  py::gil_scoped_release nogil;
-  return mbh::sample_obstacles(reinterpret_cast<float*>(out), B, n_obs, points, dim, L, (uint64_t)seed,
-                               reinterpret_cast<const float*>(circle), reinterpret_cast<const float*>(rect),
-                               reinterpret_cast<const float*>(sphere));
+static float min_pair_distance(py::kwargs kw) {
+  Args x("min_pair_distance", kw);
+  return x.then(nogil(mbh::min_pair_distance), x.ptr<const float>("p"), x.i("n"), x.i("dim"), x.i("stride"),
+                x.f("L"), x.f("cutoff"));
+}
+
+static int sample_obstacles(py::kwargs kw) {
+  Args x("sample_obstacles", kw);
+  return x.then(nogil(mbh::sample_obstacles), x.ptr<float>("out"), x.i("B"), x.i("n_obs"), x.i("points"), x.i("dim"),
+                x.f("L"), (uint64_t)x.u("seed"), x.ptr<const float>("circle"), x.ptr<const float>("rect"),
+                x.ptr<const float>("sphere"));
 }
 
 PYBIND11_MODULE(_host, m) {

@@ -24,54 +24,42 @@
 #include <vector>
 
 #include "args.h"
-
-namespace py = pybind11;
-using u64 = unsigned long long;
+#include "pyargs.h"
 
 namespace {
 
-template <typename T>
-T* P(u64 p) { return reinterpret_cast<T*>(static_cast<uintptr_t>(p)); }
 hipStream_t ST(u64 s) { return reinterpret_cast<hipStream_t>(static_cast<uintptr_t>(s)); }
-
-void chk(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-void chk(int rc, const char* what) {
-  if (rc != 0) throw std::runtime_error(std::string(what) + " launch failed: " + std::to_string(rc));
-}
 
 class RolloutDriver {
  public:
-  explicit RolloutDriver(py::dict c) {
-    auto I = [&](const char* k) { return c[k].cast<long>(); };
-    auto F = [&](const char* k) { return c[k].cast<float>(); };
-    auto U = [&](const char* k) { return c[k].cast<u64>(); };
-    B_ = (int)I("B"); N_ = (int)I("N"); Nn_ = (int)I("Nn"); K_ = (int)I("K"); D_ = (int)I("D");
+  // (no Args::done() here or in BpttDriver: the engine passes diagnostic keys that not every build reads)
+  explicit RolloutDriver(py::dict cfg) {
+    Args c("RolloutDriver", cfg);
+    c("B", B_); c("N", N_); c("Nn", Nn_); c("K", K_); c("D", D_);
     W_ = D_ == 2 ? 4 : 8;
-    Tmax_ = (int)I("Tmax"); num_cu_ = (int)I("num_cu"); prec_ = (int)I("prec"); prow_ = prec_ == 2 ? 256 : 128;
-    resort_ = (int)I("resort_every"); safety_ = (int)I("compute_safety"); overlap_ = (int)I("overlap_hfwd");
-    hfwd_blocks_ = (int)I("hfwd_blocks");
-    L_ = F("L");
-    S_ = U("S"); G_ = U("G"); A_ = U("A"); idx_ = U("idx"); dang_ = U("dang"); cnt_ = U("cnt");
-    safe_ = U("safe"); dist_ = U("dist"); act_ = U("act"); pooled_ = U("pooled"); argmax_ = U("argmax");
-    perm_ = U("perm"); host_dist_ = U("host_dist");
-    ctrl_w_ = U("ctrl_w"); f_edge_ = (int)I("f_edge"); f_node_ = (int)I("f_node"); ctrl_v_ = U("ctrl_v");
-    cbf_w_ = U("cbf_w"); f_fwd_ = (int)I("f_fwd"); cbf_rm_ = U("cbf_rm"); cbf_v_ = U("cbf_v");
-    hbuf_ = U("hbuf"); hmask_ = U("hmask"); src_ = U("src"); nev_ = U("nev");
-    r2_train_ = F("r2_train"); ttc_train_ = F("ttc_train"); r2_check_ = F("r2_check"); ttc_check_ = F("ttc_check");
-    dt_ = F("dt"); obs_r_ = F("obs_r"); sqrt3_ = F("sqrt3"); dist_thr_ = F("dist_thr"); dist_eps_ = F("dist_eps");
-    done_thr_ = F("done_thr");
-    check_ = (int)I("check_every");
-    noise_key_ = U("noise_key"); noise_prob_ = F("noise_prob"); noise_scale_ = F("noise_scale");
-    scan_ws_ = U("scan_ws"); scan_ws_env_ = I("scan_ws_env");
-    apw_ = (int)I("apw");
-    small_ctl_ = U("small_ctl"); small_apw_ = (int)I("small_apw"); knn_tail_ = (int)I("knn_tail");
-    small_stamps_ = c.contains("small_stamps") ? U("small_stamps") : 0;
+    c("Tmax", Tmax_); c("num_cu", num_cu_); c("prec", prec_); prow_ = prec_ == 2 ? 256 : 128;
+    c("resort_every", resort_); c("compute_safety", safety_); c("overlap_hfwd", overlap_);
+    c("hfwd_blocks", hfwd_blocks_);
+    c("L", L_);
+    c("S", S_); c("G", G_); c("A", A_); c("idx", idx_); c("dang", dang_); c("cnt", cnt_);
+    c("safe", safe_); c("dist", dist_); c("act", act_); c("pooled", pooled_); c("argmax", argmax_);
+    c("perm", perm_); c("host_dist", host_dist_);
+    c("ctrl_w", ctrl_w_); c("f_edge", f_edge_); c("f_node", f_node_); c("ctrl_v", ctrl_v_);
+    c("cbf_w", cbf_w_); c("f_fwd", f_fwd_); c("cbf_rm", cbf_rm_); c("cbf_v", cbf_v_);
+    c("hbuf", hbuf_); c("hmask", hmask_); c("src", src_); c("nev", nev_);
+    c("r2_train", r2_train_); c("ttc_train", ttc_train_); c("r2_check", r2_check_); c("ttc_check", ttc_check_);
+    c("dt", dt_); c("obs_r", obs_r_); c("sqrt3", sqrt3_); c("dist_thr", dist_thr_); c("dist_eps", dist_eps_);
+    c("done_thr", done_thr_);
+    c("check_every", check_);
+    c("noise_key", noise_key_); c("noise_prob", noise_prob_); c("noise_scale", noise_scale_);
+    c("scan_ws", scan_ws_); c("scan_ws_env", scan_ws_env_);
+    c("apw", apw_);
+    c("small_ctl", small_ctl_); c("small_apw", small_apw_); c("knn_tail", knn_tail_);
+    c.opt("small_stamps", small_stamps_);
     // the node MLP's activations per step (T, B*N, node_act_bytes), kept for the cooperative node
     // backward (0 = not kept)
-    acts_ = c.contains("node_acts") ? U("node_acts") : 0;
-    act_bytes_ = c.contains("node_act_bytes") ? I("node_act_bytes") : 0;
+    c.opt("node_acts", acts_);
+    c.opt("node_act_bytes", act_bytes_);
     if (small_ctl_) {
       chk(hipHostMalloc((void**)&small_res_, 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
       small_res_[0] = small_res_[1] = 0;
@@ -79,8 +67,8 @@ class RolloutDriver {
     }
     // early-stop publication (ctrl.hip publish_step): per-step workgroup counters on the device,
     // the per-env sums and a flag per step in host-coherent memory
-    publish_ = c.contains("publish") ? (int)I("publish") : 0;
-    poll_query_ms_ = c.contains("poll_query_ms") ? (int)I("poll_query_ms") : 100;
+    c.opt("publish", publish_);
+    c.opt("poll_query_ms", poll_query_ms_);
     if (publish_) {
       const size_t nd = (size_t)Tmax_ * B_, bytes = nd * sizeof(unsigned long long) + (size_t)Tmax_ * sizeof(unsigned);
       chk(hipHostMalloc((void**)&pub_host_, bytes, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
@@ -97,7 +85,7 @@ class RolloutDriver {
     // stream -> stream dependencies on one device: a device-scope release is enough (the default
     // system-scope fence writes back / invalidates caches for host visibility and stalls the
     // queue behind it); the copy-completion events the host waits on keep the system fence
-    const unsigned fork_flags = hipEventDisableTiming | (c["fork_device_scope"].cast<int>() ? hipEventReleaseToDevice : 0u);
+    const unsigned fork_flags = hipEventDisableTiming | (c.i("fork_device_scope") ? hipEventReleaseToDevice : 0u);
     chk(hipEventCreateWithFlags(&ev_main_, fork_flags), "hipEventCreate");
     chk(hipEventCreateWithFlags(&ev_side_, fork_flags), "hipEventCreate");
   }
@@ -221,7 +209,7 @@ class RolloutDriver {
     a.res_gen = (int)++small_gen_;
     a.s0 = P<const float>(s0); a.g0 = P<const float>(g0);
     if ((s0 == 0) != (g0 == 0)) throw std::invalid_argument("run_small: s0 and g0 go together");
-    chk((prec_ == 2 ? mb_rollout_small_x3 : prec_ == 1 ? mb_rollout_small_f16 : mb_rollout_small)(&a, st), "rollout_small");
+    chk(by_prec(prec_, mb_rollout_small, mb_rollout_small_f16, mb_rollout_small_x3)(&a, st), "rollout_small");
     // the horizon arrives in host-coherent memory when the last workgroup finishes: poll it (a
     // stream synchronisation added a memset, a read-back copy and the blocking wake-up to every
     // iteration of the small configurations)
@@ -344,7 +332,7 @@ class RolloutDriver {
     a.pooled = P<h16>(pooled_) + (long)t * B_ * N_ * prow_; a.p_env = (long)N_ * prow_;
     a.argmax = P<uint8_t>(argmax_) + (long)t * B_ * N_ * 128; a.am_env = (long)N_ * 128;
     a.apw = apw_;
-    chk((prec_ == 2 ? mb_ctrl_fwd_x3 : prec_ == 1 ? mb_ctrl_fwd_f16 : mb_ctrl_fwd)(&a, num_cu_, st), "ctrl_fwd");
+    chk(by_prec(prec_, mb_ctrl_fwd, mb_ctrl_fwd_f16, mb_ctrl_fwd_x3)(&a, num_cu_, st), "ctrl_fwd");
   }
 
   // CBF h of the main slots of step t, evaluations [t*BNK, (t+1)*BNK), on the side stream
@@ -360,13 +348,13 @@ class RolloutDriver {
     a.h_out = P<float>(hbuf_); a.mask_out = P<uint8_t>(hmask_);
     a.obs_r = obs_r_; a.dist_thr = dist_thr_; a.dist_eps = dist_eps_;
     a.u_begin = (unsigned)(t * bnk); a.u_end = (unsigned)((t + 1) * bnk);
-    chk((prec_ == 2 ? mb_cbf_hfwd_x3 : prec_ == 1 ? mb_cbf_hfwd_f16 : mb_cbf_hfwd)(&a, hfwd_blocks_, hs), "cbf_hfwd");
+    chk(by_prec(prec_, mb_cbf_hfwd, mb_cbf_hfwd_f16, mb_cbf_hfwd_x3)(&a, hfwd_blocks_, hs), "cbf_hfwd");
   }
 
   int B_, N_, Nn_, K_, D_, W_, Tmax_, num_cu_, prec_, prow_, resort_, safety_, overlap_, hfwd_blocks_, check_, apw_;
   int publish_ = 0;
   unsigned gen_ = 0;
-  int poll_query_ms_ = 0;
+  int poll_query_ms_ = 100;
   unsigned long long* pub_host_ = nullptr;   // host view: [Tmax][B] sums, then [Tmax] flags
   unsigned long long* pub_dev_ = nullptr;    // the same memory, device view
   unsigned* pub_ctr_ = nullptr;              // [Tmax] per-step workgroup counters (device)
@@ -399,37 +387,35 @@ class RolloutDriver {
 // for small scenes (BASELINE config #2: 32 agents), where Python paid ~15 us per launch.
 class BpttDriver {
  public:
-  explicit BpttDriver(py::dict c) {
-    auto I = [&](const char* k) { return c[k].cast<long>(); };
-    auto F = [&](const char* k) { return c[k].cast<float>(); };
-    auto U = [&](const char* k) { return c[k].cast<u64>(); };
-    B_ = (int)I("B"); N_ = (int)I("N"); Nn_ = (int)I("Nn"); K_ = (int)I("K"); D_ = (int)I("D");
+  explicit BpttDriver(py::dict cfg) {
+    Args c("BpttDriver", cfg);
+    c("B", B_); c("N", N_); c("Nn", Nn_); c("K", K_); c("D", D_);
     R_ = D_ == 2 ? 1 : 2;
-    Tmax_ = (int)I("Tmax"); prec_ = (int)I("prec"); prow_ = prec_ == 2 ? 256 : 128; nb_node_ = (int)I("nb_node"); nb_edge_ = (int)I("nb_edge");
-    qsplit_ = (int)I("qsplit");
-    pooled_ = U("pooled"); S_ = U("S"); G_ = U("G"); A_ = U("A"); dS_ = U("dS"); Gb_ = U("Gb"); valid_ = U("valid");
-    idx_ = U("idx"); argmax_ = U("argmax"); rptr_ = U("rptr"); redges_ = U("redges");
-    wrm_ = U("ctrl_rm"); o1_ = (int)I("o_w1"); o2_ = (int)I("o_w2"); o3_ = (int)I("o_w3"); o4_ = (int)I("o_w4");
-    wvec_ = U("ctrl_v"); act_scale_ = U("act_scale"); dP_ = U("dP"); ego_ = U("ego"); dEc_ = U("dEc");
-    part_node_ = U("part_node"); part_edge_ = U("part_edge");
-    wpack_ = U("ctrl_w"); f_ew1f_ = (int)I("f_ew1f"); f_ew2tn_ = (int)I("f_ew2tn");
-    dt_ = F("dt"); sqrt3_ = F("sqrt3");
-    node_chunk_ = (int)I("node_chunk");
+    c("Tmax", Tmax_); c("prec", prec_); prow_ = prec_ == 2 ? 256 : 128; c("nb_node", nb_node_); c("nb_edge", nb_edge_);
+    c("qsplit", qsplit_);
+    c("pooled", pooled_); c("S", S_); c("G", G_); c("A", A_); c("dS", dS_); c("Gb", Gb_); c("valid", valid_);
+    c("idx", idx_); c("argmax", argmax_); c("rptr", rptr_); c("redges", redges_);
+    c("ctrl_rm", wrm_); c("o_w1", o1_); c("o_w2", o2_); c("o_w3", o3_); c("o_w4", o4_);
+    c("ctrl_v", wvec_); c("act_scale", act_scale_); c("dP", dP_); c("ego", ego_); c("dEc", dEc_);
+    c("part_node", part_node_); c("part_edge", part_edge_);
+    c("ctrl_w", wpack_); c("f_ew1f", f_ew1f_); c("f_ew2tn", f_ew2tn_);
+    c("dt", dt_); c("sqrt3", sqrt3_);
+    c("node_chunk", node_chunk_);
     // per-step slab rows (small grids): step t's node / edge workgroups write rows (T-1-t) x grid
     // of the slabs instead of accumulating into one row per workgroup
-    step_rows_ = c.contains("step_rows") ? (int)I("step_rows") : 0;
-    acts_ = c.contains("node_acts") ? U("node_acts") : 0;
-    act_bytes_ = c.contains("node_act_bytes") ? I("node_act_bytes") : 0;
-    node_part_ = c.contains("node_part") ? I("node_part") : 0;
-    edge_part_ = c.contains("edge_part") ? I("edge_part") : 0;
+    c.opt("step_rows", step_rows_);
+    c.opt("node_acts", acts_);
+    c.opt("node_act_bytes", act_bytes_);
+    c.opt("node_part", node_part_);
+    c.opt("edge_part", edge_part_);
     if (step_rows_ && (node_part_ <= 0 || edge_part_ <= 0))
       throw std::invalid_argument("BpttDriver: step_rows needs the slab row sizes");
-    fused_ = c.contains("fused_step") ? (int)I("fused_step") : 0;
+    c.opt("fused_step", fused_);
     if (fused_ && (node_chunk_ != 32 || nb_node_ != nb_edge_))
       throw std::invalid_argument("BpttDriver: the fused step needs 32-agent chunks and one grid");
-    gscale_ = c.contains("gscale") ? U("gscale") : 0;   // fp16: device loss scale (or 0)
-    ew16_ = c.contains("ctrl_w16") ? U("ctrl_w16") : 0;   // K = 12: 16x16x32 edge backward fragments
-    nw16_ = c.contains("node_rm16") ? U("node_rm16") : 0;  // 128-agent chunks: 16x16x32 node backward images
+    c.opt("gscale", gscale_);       // fp16: device loss scale (or 0)
+    c.opt("ctrl_w16", ew16_);       // K = 12: 16x16x32 edge backward fragments
+    c.opt("node_rm16", nw16_);      // 128-agent chunks: 16x16x32 node backward images
     if (nw16_ && (node_chunk_ != 128 || fused_))
       throw std::invalid_argument("BpttDriver: the 16x16x32 node backward needs 128-agent chunks");
     if (B_ < 1 || N_ < 1 || Nn_ < N_ || K_ < 1 || K_ > 16 || (D_ != 2 && D_ != 3) || Tmax_ < 1 || nb_node_ < 1 ||
@@ -505,12 +491,12 @@ class BpttDriver {
         a.w16 = fused_ ? nullptr : P<const h16>(ew16_);   // (the fused step keeps its own edge phase)
       }
       if (fused_) {      // node + edge backward of the same 32-agent chunks in one launch
-        chk((prec_ == 2 ? mb_ctrl_bwd_step_x3 : prec_ == 1 ? mb_ctrl_bwd_step_f16 : mb_ctrl_bwd_step)(&na, &ea, nb_node_, st),
+        chk(by_prec(prec_, mb_ctrl_bwd_step, mb_ctrl_bwd_step_f16, mb_ctrl_bwd_step_x3)(&na, &ea, nb_node_, st),
             "ctrl_bwd_step");
       } else {
-        chk((prec_ == 2 ? mb_ctrl_node_bwd_x3 : prec_ == 1 ? mb_ctrl_node_bwd_f16 : mb_ctrl_node_bwd)(&na, nb_node_, st),
+        chk(by_prec(prec_, mb_ctrl_node_bwd, mb_ctrl_node_bwd_f16, mb_ctrl_node_bwd_x3)(&na, nb_node_, st),
             "ctrl_node_bwd");
-        chk((prec_ == 2 ? mb_ctrl_edge_bwd_x3 : prec_ == 1 ? mb_ctrl_edge_bwd_f16 : mb_ctrl_edge_bwd)(&ea, nb_edge_, st),
+        chk(by_prec(prec_, mb_ctrl_edge_bwd, mb_ctrl_edge_bwd_f16, mb_ctrl_edge_bwd_x3)(&ea, nb_edge_, st),
             "ctrl_edge_bwd");
       }
       // (no combine launch: the next step's node backward forms G_t in its prologue; G_0 = dL/ds_0
@@ -529,43 +515,51 @@ class BpttDriver {
   float dt_, sqrt3_;
 };
 
+// One call of the safety filter: the kernels' arguments (all but r.it) and how they are launched
+struct RefineCall {
+  mb::RefineSmallArgs sa;       // sa.r: both filters; sa.ew: the persistent filter's result words
+  int num_blocks, prec;         // num_blocks: refine_grad's grid (the loop filter's alone, as r.dEv and r.ctl)
+};
+
+RefineCall refine_call(Args& x) {
+  RefineCall c{};
+  mb::RefineArgs& r = c.sa.r;
+  x("S", r.S); x("s_env", r.s_env); x("dim", r.dim); x("idx", r.idx); x("a", r.a); x("delta", r.delta);
+  x("h", r.h); x("B", r.B); x("N", r.N); x("Nn", r.Nn); x("K", r.K); x("wpack", r.wpack);
+  x("f_bwd", r.f_bwd); x("wrm", r.wrm); x("wvec", r.wvec); x("ptr", r.ptr); x("edges", r.edges);
+  x.opt("dEv", r.dEv); x.opt("ctl", r.ctl); x("dt", r.dt); x("dt_alpha", r.dt_alpha); x("lr", r.lr);
+  x("obs_r", r.obs_r); x("dist_thr", r.dist_thr); x("dist_eps", r.dist_eps); x("hn_out", r.hn_out);
+  x("flag_out", r.flag_out); x("env_active", r.env_active); x("loops", c.sa.loops); x.opt("ew", c.sa.ew);
+  x.opt("num_blocks", c.num_blocks); x("prec", c.prec);
+  return c;
+}
+
 // Safety-filter loop (csrc/refine.hip): `loops` x (refine_grad, refine_update) on the caller's
 // stream. The pointers and sizes are validated once; the control words (2 per iteration) are
 // cleared here; nothing is allocated or built; no host synchronisation -- the early-out lives in the
-// kernels. hn_out / flag_out (optional) receive the first iteration's h(s') and hinge flags.
-// env_active (optional, (B,) bytes on the device) is handed to the kernels as it is: never read here.
-int refine_loop(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, int B, int N, int Nn, int K, u64 wpack,
-                int f_bwd, u64 wrm, u64 wvec, u64 dEv, u64 ptr, u64 edges, u64 ctl, int loops, float dt, float dt_alpha,
-                float lr, float obs_r, float dist_thr, float dist_eps, u64 hn_out, u64 flag_out, u64 env_active,
-                int num_blocks, int prec, u64 stream) {
-  if (dim != 2 && dim != 3) return -1;
-  if (B < 1 || N < 1 || Nn < N || K < 1 || K > 16 || loops < 0 || num_blocks < 1 || f_bwd < 0 || s_env < Nn) return -1;
-  if (prec < 0 || prec > 2) return -1;
-  if (!S || !idx || !a || !delta || !h || !wpack || !wrm || !wvec || !dEv || !ptr || !edges || !ctl) return -2;
+// kernels. r.hn_out / r.flag_out (optional) receive the first iteration's h(s') and hinge flags.
+// r.env_active (optional, (B,) bytes on the device) is handed to the kernels as it is: never read here.
+int refine_loop(const RefineCall* c, hipStream_t st) {
+  mb::RefineArgs r = c->sa.r;
+  const int loops = c->sa.loops;
+  if ((r.dim != 2 && r.dim != 3) || r.B < 1 || r.N < 1 || r.Nn < r.N || r.K < 1 || r.K > 16 || loops < 0 ||
+      c->num_blocks < 1 || r.f_bwd < 0 || r.s_env < r.Nn || c->prec < 0 || c->prec > 2)
+    return -1;
+  if (!r.S || !r.idx || !r.a || !r.delta || !r.h || !r.wpack || !r.wrm || !r.wvec || !r.dEv || !r.ptr || !r.edges || !r.ctl)
+    return -2;
   if (loops == 0) return 0;
-  hipStream_t st = ST(stream);
-  mb::RefineArgs r{};
-  r.S = P<const float4>(S); r.s_env = s_env; r.dim = dim; r.idx = P<const int>(idx);
-  r.a = P<const float>(a); r.delta = P<float>(delta); r.h = P<const float>(h);
-  r.B = B; r.N = N; r.Nn = Nn; r.K = K;
-  r.wpack = P<const h16>(wpack); r.f_bwd = f_bwd; r.wrm = P<const h16>(wrm); r.wvec = P<const float>(wvec);
-  r.dEv = P<float>(dEv); r.ptr = P<const int>(ptr); r.edges = P<const int>(edges);
-  r.ctl = P<unsigned long long>(ctl);
-  r.env_active = P<const uint8_t>(env_active);
-  r.dt = dt; r.dt_alpha = dt_alpha; r.lr = lr; r.obs_r = obs_r; r.dist_thr = dist_thr; r.dist_eps = dist_eps;
   const hipError_t e = hipMemsetAsync(r.ctl, 0, (size_t)loops * 2 * sizeof(unsigned long long), st);
   if (e != hipSuccess) return (int)e;
-  const auto grad = prec == 2 ? mb_refine_grad_x3 : prec == 1 ? mb_refine_grad_f16 : mb_refine_grad;
-  const int pr = (prec == 2 ? mb_refine_prepare_x3 : prec == 1 ? mb_refine_prepare_f16 : mb_refine_prepare)(dim);
+  const auto grad = by_prec(c->prec, mb_refine_grad, mb_refine_grad_f16, mb_refine_grad_x3);
+  const int pr = by_prec(c->prec, mb_refine_prepare, mb_refine_prepare_f16, mb_refine_prepare_x3)(r.dim);
   if (pr) return pr;
-  for (int it = 0; it < loops; ++it) {
-    r.it = it;
-    r.hn_out = it == 0 ? P<float>(hn_out) : nullptr;
-    r.flag_out = it == 0 ? P<uint8_t>(flag_out) : nullptr;
-    int rc = grad(&r, num_blocks, st);
+  for (r.it = 0; r.it < loops; ++r.it) {
+    int rc = grad(&r, c->num_blocks, st);
     if (rc) return rc;
     rc = mb_refine_update(&r, st);
     if (rc) return rc;
+    r.hn_out = nullptr;
+    r.flag_out = nullptr;
   }
   return 0;
 }
@@ -573,30 +567,28 @@ int refine_loop(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, in
 // Persistent safety filter for small envs (csrc/refine.hip refine_small_kernel): the whole loop of
 // every env in ONE launch on the caller's stream, one workgroup per env. The pointers and sizes are
 // validated once; the kernel's dynamic-LDS attribute is set by its launcher; nothing is allocated
-// or cleared here (delta and ew (B, loops, 2) arrive zeroed); no host synchronisation.
-int refine_small(u64 S, long s_env, int dim, u64 idx, u64 a, u64 delta, u64 h, int B, int N, int Nn, int K, u64 wpack,
-                 int f_bwd, u64 wrm, u64 wvec, u64 ptr, u64 edges, u64 ew, int loops, float dt, float dt_alpha,
-                 float lr, float obs_r, float dist_thr, float dist_eps, u64 hn_out, u64 flag_out, u64 env_active,
-                 int prec, u64 stream) {
-  if (dim != 2 && dim != 3) return -1;
-  if (B < 1 || N < 1 || Nn < N || K < 1 || K > 16 || loops < 0 || f_bwd < 0 || s_env < Nn) return -1;
-  if (Nn > 64) return -4;                                      // SMALL_MAXN: the env must fit one workgroup's LDS
-  if (prec < 0 || prec > 2) return -1;
-  if (!S || !idx || !a || !delta || !h || !wpack || !wrm || !wvec || !ptr || !edges || !ew) return -2;
-  if (loops == 0) return 0;
-  mb::RefineSmallArgs sa{};
-  mb::RefineArgs& r = sa.r;
-  r.S = P<const float4>(S); r.s_env = s_env; r.dim = dim; r.idx = P<const int>(idx);
-  r.a = P<const float>(a); r.delta = P<float>(delta); r.h = P<const float>(h);
-  r.B = B; r.N = N; r.Nn = Nn; r.K = K;
-  r.wpack = P<const h16>(wpack); r.f_bwd = f_bwd; r.wrm = P<const h16>(wrm); r.wvec = P<const float>(wvec);
-  r.ptr = P<const int>(ptr); r.edges = P<const int>(edges);
-  r.env_active = P<const uint8_t>(env_active);
-  r.dt = dt; r.dt_alpha = dt_alpha; r.lr = lr; r.obs_r = obs_r; r.dist_thr = dist_thr; r.dist_eps = dist_eps;
-  r.hn_out = P<float>(hn_out); r.flag_out = P<uint8_t>(flag_out);     // the kernel writes them at iteration 0 only
-  sa.loops = loops;
-  sa.ew = P<unsigned long long>(ew);
-  return (prec == 2 ? mb_refine_small_x3 : prec == 1 ? mb_refine_small_f16 : mb_refine_small)(&sa, ST(stream));
+// or cleared here (delta and ew (B, loops, 2) arrive zeroed); no host synchronisation. The kernel
+// writes r.hn_out / r.flag_out at iteration 0 only.
+int refine_small(const RefineCall* c, hipStream_t st) {
+  const mb::RefineArgs& r = c->sa.r;
+  if (r.dim != 2 && r.dim != 3) return -1;
+  if (r.B < 1 || r.N < 1 || r.Nn < r.N || r.K < 1 || r.K > 16 || c->sa.loops < 0 || r.f_bwd < 0 || r.s_env < r.Nn) return -1;
+  if (r.Nn > 64) return -4;                                    // SMALL_MAXN: the env must fit one workgroup's LDS
+  if (c->prec < 0 || c->prec > 2) return -1;
+  if (!r.S || !r.idx || !r.a || !r.delta || !r.h || !r.wpack || !r.wrm || !r.wvec || !r.ptr || !r.edges || !c->sa.ew) return -2;
+  if (c->sa.loops == 0) return 0;
+  return by_prec(c->prec, mb_refine_small, mb_refine_small_f16, mb_refine_small_x3)(&c->sa, st);
+}
+
+// The arguments of the three launches of csrc/episode.hip (the driver sets S_cur / S_next per step)
+mb::EpisodeArgs episode_args(Args& x) {
+  mb::EpisodeArgs e{};
+  x.opt("S_cur", e.S_cur); x.opt("S_next", e.S_next); x("s_env", e.s_env); x("dim", e.dim); x("B", e.B);
+  x("N", e.N); x("A", e.A); x("delta", e.delta); x("G", e.G); x("dt", e.dt); x("st", e.st);
+  x("dist_fx", e.dist_fx); x("safe", e.safe); x("active", e.active); x("prev_active", e.prev_active);
+  x("ctl", e.ctl); x("ew", e.ew); x("loops", e.loops); x("mode", e.mode); x("thr", e.thr); x("out", e.out);
+  e.thr_fx = (unsigned long long)std::llrint((double)e.thr * (double)e.N * mb::FX_DIST);
+  return e;
 }
 
 // Closed-loop episode driver (csrc/episode.hip): a whole batch of episodes -- validation during
@@ -622,15 +614,14 @@ class EpisodeDriver {
   EpisodeDriver& operator=(const EpisodeDriver&) = delete;
 
   struct Cfg {
-    int B, N, Nn, K, D, num_cu, prec_ctrl, prec_cbf, apw, max_steps, check_every;
-    int refine, persistent, loops, mask_done, cbf_blocks, refine_blocks;
-    int f_edge, f_node, f_cbf;
-    float L, r2_train, ttc_train, r2_check, ttc_check, dt, dt_alpha, lr, obs_r, sqrt3, dist_thr, dist_eps, done_thr;
-    u64 S0, S1, G, idx, A, pooled, argmax, perm, safe, st, dist_fx, active, prev_active, out;
-    u64 ctrl_w, ctrl_v, cbf_w, cbf_rm, cbf_v, delta, h, rptr, redges, csr_ws, dEv, ctl, ew, scan_ws;
+    mb::EpisodeArgs e;          // all but S_cur / S_next (per step); e.mode != 0: the filter runs
+    RefineCall r;               // the filter's, all but S (per step)
+    int Nn, K, num_cu, prec_ctrl, apw, max_steps, check_every, mask_done, cbf_blocks, f_edge, f_node;
+    float L, r2_train, ttc_train, r2_check, ttc_check, obs_r, sqrt3;
+    u64 S0, S1, idx, pooled, argmax, perm, ctrl_w, ctrl_v, csr_ws, scan_ws;
     long scan_ws_env;
     mb::LossConsts lc;
-    u64 stream;
+    hipStream_t stream;
   };
 
   // Returns (steps issued, 0 or 1: the buffer that holds the final state).
@@ -641,77 +632,65 @@ class EpisodeDriver {
   }
 
  private:
+  // cfg: the driver's own keys, "episode": the EpisodeArgs fields, "refine": the RefineArgs fields or None
   static Cfg parse(const py::dict& c) {
-    auto I = [&](const char* k) { return c[k].cast<long>(); };
-    auto F = [&](const char* k) { return c[k].cast<float>(); };
-    auto U = [&](const char* k) { return c[k].cast<u64>(); };
+    Args x("EpisodeDriver", c);
     Cfg g{};
-    g.B = (int)I("B"); g.N = (int)I("N"); g.Nn = (int)I("Nn"); g.K = (int)I("K"); g.D = (int)I("D");
-    g.num_cu = (int)I("num_cu"); g.prec_ctrl = (int)I("prec_ctrl"); g.prec_cbf = (int)I("prec_cbf"); g.apw = (int)I("apw");
-    g.max_steps = (int)I("max_steps"); g.check_every = (int)I("check_every");
-    g.refine = (int)I("refine"); g.persistent = (int)I("persistent"); g.loops = (int)I("loops");
-    g.mask_done = (int)I("mask_done"); g.cbf_blocks = (int)I("cbf_blocks"); g.refine_blocks = (int)I("refine_blocks");
-    g.f_edge = (int)I("f_edge"); g.f_node = (int)I("f_node"); g.f_cbf = (int)I("f_cbf");
-    g.L = F("L"); g.r2_train = F("r2_train"); g.ttc_train = F("ttc_train"); g.r2_check = F("r2_check");
-    g.ttc_check = F("ttc_check"); g.dt = F("dt"); g.dt_alpha = F("dt_alpha"); g.lr = F("lr"); g.obs_r = F("obs_r");
-    g.sqrt3 = F("sqrt3"); g.dist_thr = F("dist_thr"); g.dist_eps = F("dist_eps"); g.done_thr = F("done_thr");
-    g.S0 = U("S0"); g.S1 = U("S1"); g.G = U("G"); g.idx = U("idx"); g.A = U("A"); g.pooled = U("pooled");
-    g.argmax = U("argmax"); g.perm = U("perm"); g.safe = U("safe"); g.st = U("st"); g.dist_fx = U("dist_fx");
-    g.active = U("active"); g.prev_active = U("prev_active"); g.out = U("out");
-    g.ctrl_w = U("ctrl_w"); g.ctrl_v = U("ctrl_v"); g.cbf_w = U("cbf_w"); g.cbf_rm = U("cbf_rm"); g.cbf_v = U("cbf_v");
-    g.delta = U("delta"); g.h = U("h"); g.rptr = U("rptr"); g.redges = U("redges"); g.csr_ws = U("csr_ws");
-    g.dEv = U("dEv"); g.ctl = U("ctl"); g.ew = U("ew"); g.scan_ws = U("scan_ws"); g.scan_ws_env = I("scan_ws_env");
-    const py::tuple lc = c["loss_consts"].cast<py::tuple>();
-    if (lc.size() < 7) throw std::invalid_argument("EpisodeDriver: loss_consts needs 7 values");
-    g.lc.eps_dang = lc[0].cast<float>(); g.lc.dt_alpha = lc[1].cast<float>(); g.lc.w_dang = lc[2].cast<float>();
-    g.lc.w_safe = lc[3].cast<float>(); g.lc.w_dang_d = lc[4].cast<float>(); g.lc.w_safe_d = lc[5].cast<float>();
-    g.lc.scale = lc[6].cast<float>();
-    g.stream = U("stream");
-    if (g.B < 1 || g.N < 1 || g.Nn < g.N || g.K < 1 || g.K > 16 || g.K > g.Nn || (g.D != 2 && g.D != 3) ||
-        g.max_steps < 0 || g.loops < 0 || g.prec_ctrl < 0 || g.prec_ctrl > 2 || g.prec_cbf < 0 || g.prec_cbf > 2)
+    bool none = false;
+    Args ex = x.sub("episode"), rx = x.sub("refine", &none);
+    g.e = episode_args(ex);
+    ex.done();
+    if (!none) g.r = refine_call(rx);
+    rx.done();
+    const mb::EpisodeArgs& e = g.e;
+    const bool filter = e.mode != 0;
+    x("Nn", g.Nn); x("K", g.K); x("num_cu", g.num_cu); x("prec_ctrl", g.prec_ctrl); x("apw", g.apw);
+    x("max_steps", g.max_steps); x("check_every", g.check_every); x("mask_done", g.mask_done);
+    x("cbf_blocks", g.cbf_blocks); x("f_edge", g.f_edge); x("f_node", g.f_node); x("L", g.L);
+    x("r2_train", g.r2_train); x("ttc_train", g.ttc_train); x("r2_check", g.r2_check); x("ttc_check", g.ttc_check);
+    x("obs_r", g.obs_r); x("sqrt3", g.sqrt3); x("S0", g.S0); x("S1", g.S1); x("idx", g.idx); x("pooled", g.pooled);
+    x("argmax", g.argmax); x("perm", g.perm); x("ctrl_w", g.ctrl_w); x("ctrl_v", g.ctrl_v); x("csr_ws", g.csr_ws);
+    x("scan_ws", g.scan_ws); x("scan_ws_env", g.scan_ws_env);
+    g.lc = x.loss_consts<mb::LossConsts>("loss_consts"); g.stream = ST(x.u("stream"));
+    x.done();
+    if (e.B < 1 || e.N < 1 || g.Nn < e.N || e.s_env != g.Nn || g.K < 1 || g.K > 16 || g.K > g.Nn || (e.dim != 2 && e.dim != 3) ||
+        g.max_steps < 0 || e.loops < 0 || e.mode < 0 || e.mode > 2 || g.prec_ctrl < 0 || g.prec_ctrl > 2 || filter == none)
       throw std::invalid_argument("EpisodeDriver: bad dimensions");
     if (g.check_every < 1) g.check_every = 1;
-    if (!g.S0 || !g.S1 || g.S0 == g.S1 || !g.G || !g.idx || !g.A || !g.argmax || !g.perm || !g.safe || !g.st ||
-        !g.dist_fx || !g.active || !g.prev_active || !g.out || !g.ctrl_w || !g.ctrl_v || (g.prec_ctrl == 2 && !g.pooled))
+    if (!g.S0 || !g.S1 || g.S0 == g.S1 || !e.G || !g.idx || !e.A || !g.argmax || !g.perm || !e.safe || !e.st ||
+        !e.dist_fx || !e.active || !e.prev_active || !e.out || !g.ctrl_w || !g.ctrl_v || (g.prec_ctrl == 2 && !g.pooled))
       throw std::invalid_argument("EpisodeDriver: a required buffer is missing");
-    if (g.refine && g.loops > 0) {
-      if (g.prec_cbf == 1) throw std::invalid_argument("EpisodeDriver: the safety filter has no fp16 build");
-      if (!g.cbf_w || !g.cbf_rm || !g.cbf_v || !g.delta || !g.h || !g.rptr || !g.redges || g.cbf_blocks < 1)
+    if (filter) {
+      const mb::RefineArgs& r = g.r.sa.r;
+      if (g.r.prec == 1) throw std::invalid_argument("EpisodeDriver: the safety filter has no fp16 build");
+      if (r.B != e.B || r.N != e.N || r.Nn != g.Nn || r.K != g.K || r.dim != e.dim || e.loops < 1 ||
+          g.r.sa.loops != e.loops || g.r.sa.ew != e.ew || g.r.prec < 0 || g.r.prec > 2 || r.idx != P<const int>(g.idx))
+        throw std::invalid_argument("EpisodeDriver: bad dimensions");
+      if (!r.wpack || !r.wrm || !r.wvec || !r.delta || r.delta != e.delta || !r.h || !r.ptr || !r.edges || g.cbf_blocks < 1)
         throw std::invalid_argument("EpisodeDriver: a filter buffer is missing");
-      if (g.persistent ? (!g.ew || g.Nn > 64) : (!g.dEv || !g.ctl || g.refine_blocks < 1))
+      if (e.mode == 2 ? (!e.ew || g.Nn > 64) : (!r.dEv || !r.ctl || g.r.num_blocks < 1))
         throw std::invalid_argument("EpisodeDriver: the filter's result words / workspace are missing");
     }
     return g;
   }
 
   std::pair<int, int> loop(const Cfg& g) {
-    hipStream_t st = ST(g.stream);
-    const bool filter = g.refine && g.loops > 0;
+    hipStream_t st = g.stream;
     u64 S[2] = {g.S0, g.S1};
     int cur = 0, t = 0;
-    mb::EpisodeArgs e{};
-    e.s_env = g.Nn; e.dim = g.D; e.B = g.B; e.N = g.N;
-    e.A = P<const float>(g.A); e.delta = filter ? P<float>(g.delta) : nullptr; e.G = P<const float>(g.G);
-    e.dt = g.dt;
-    e.st = P<long long>(g.st); e.dist_fx = P<unsigned long long>(g.dist_fx); e.safe = P<float>(g.safe);
-    e.active = P<uint8_t>(g.active); e.prev_active = P<uint8_t>(g.prev_active);
-    e.ctl = P<const unsigned long long>(g.ctl); e.ew = P<unsigned long long>(g.ew);
-    e.loops = g.loops; e.mode = !filter ? 0 : g.persistent ? 2 : 1;
-    e.thr_fx = (unsigned long long)std::llrint((double)g.done_thr * (double)g.N * mb::FX_DIST);
-    e.thr = g.done_thr;
-    e.out = P<long long>(g.out);
+    mb::EpisodeArgs e = g.e;
     for (; t < g.max_steps;) {
       scan(g, S[cur], true, st);
       ctrl(g, S[cur], st);
-      if (filter) refine(g, S[cur], st);
+      if (e.mode) refine(g, S[cur], st);
       e.S_cur = P<const float4>(S[cur]); e.S_next = P<float4>(S[cur ^ 1]);
       chk(mb_episode_advance(&e, st), "episode_advance");
       chk(mb_episode_tally(&e, st), "episode_tally");
       cur ^= 1;
       ++t;
       if (t % g.check_every == 0 && t < g.max_steps) {
-        chk(hipMemcpyAsync(alive_host_, P<const long long>(g.st) + mb::EP_ALIVE, sizeof(long long),
-                           hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        chk(hipMemcpyAsync(alive_host_, e.st + mb::EP_ALIVE, sizeof(long long), hipMemcpyDeviceToHost, st),
+            "hipMemcpyAsync");
         chk(hipStreamSynchronize(st), "hipStreamSynchronize");
         if (*alive_host_ == 0) break;
       }
@@ -723,15 +702,16 @@ class EpisodeDriver {
   }
 
   void scan(const Cfg& g, u64 S, bool knn, hipStream_t st) {
-    const int R = g.D == 2 ? 1 : 2;
+    const mb::EpisodeArgs& e = g.e;
+    const int R = e.dim == 2 ? 1 : 2;
     mb::CellSortArgs c{};
-    c.S = P<const float4>(S); c.s_env = g.Nn; c.B = g.B; c.N = g.Nn; c.L = g.L; c.perm = P<int>(g.perm); c.rec = R;
+    c.S = P<const float4>(S); c.s_env = g.Nn; c.B = e.B; c.N = g.Nn; c.L = g.L; c.perm = P<int>(g.perm); c.rec = R;
     chk(mb_cell_sort(&c, st), "cell_sort");
     mb::ScanArgs a{};
     a.S = P<const float4>(S); a.s_env = g.Nn; a.perm = P<const int>(g.perm);
-    a.B = g.B; a.N = g.N; a.K = knn ? g.K : 1; a.Nn = g.Nn; a.dim = g.D;
-    a.idx = knn ? P<int>(g.idx) : nullptr; a.i_env = knn ? (long)g.N * g.K : 0;
-    a.safe = P<float>(g.safe); a.sf_env = 1;
+    a.B = e.B; a.N = e.N; a.K = knn ? g.K : 1; a.Nn = g.Nn; a.dim = e.dim;
+    a.idx = knn ? P<int>(g.idx) : nullptr; a.i_env = knn ? (long)e.N * g.K : 0;
+    a.safe = e.safe; a.sf_env = 1;
     a.r2_train = g.r2_train; a.ttc_train = g.ttc_train; a.r2_check = g.r2_check; a.ttc_check = g.ttc_check;
     a.do_knn = knn ? 1 : 0; a.do_safety = 1;
     a.ws = P<float4>(g.scan_ws); a.ws_env = g.scan_ws_env;
@@ -739,72 +719,55 @@ class EpisodeDriver {
   }
 
   void ctrl(const Cfg& g, u64 S, hipStream_t st) {
+    const mb::EpisodeArgs& e = g.e;
     const int prow = g.prec_ctrl == 2 ? 256 : 128;
     mb::CtrlArgs a{};
-    a.dim = g.D; a.apw = g.apw;
-    a.S = P<const float4>(S); a.s_env = g.Nn; a.G = P<const float>(g.G);
-    a.idx = P<const int>(g.idx); a.i_env = (long)g.N * g.K;
-    a.B = g.B; a.N = g.N; a.K = g.K;
+    a.dim = e.dim; a.apw = g.apw;
+    a.S = P<const float4>(S); a.s_env = g.Nn; a.G = e.G;
+    a.idx = P<const int>(g.idx); a.i_env = (long)e.N * g.K;
+    a.B = e.B; a.N = e.N; a.K = g.K;
     a.wpack = P<const h16>(g.ctrl_w); a.f_edge = g.f_edge; a.f_node = g.f_node; a.wvec = P<const float>(g.ctrl_v);
-    a.A = P<float>(g.A); a.a_env = g.N;
-    a.dt = g.dt; a.obs_r = g.obs_r; a.sqrt3 = g.sqrt3;
-    a.pooled = P<h16>(g.pooled); a.p_env = (long)g.N * prow;
-    a.argmax = P<uint8_t>(g.argmax); a.am_env = (long)g.N * 128;
-    chk((g.prec_ctrl == 2 ? mb_ctrl_fwd_x3 : g.prec_ctrl == 1 ? mb_ctrl_fwd_f16 : mb_ctrl_fwd)(&a, g.num_cu, st), "ctrl_fwd");
+    a.A = const_cast<float*>(e.A); a.a_env = e.N;
+    a.dt = e.dt; a.obs_r = g.obs_r; a.sqrt3 = g.sqrt3;
+    a.pooled = P<h16>(g.pooled); a.p_env = (long)e.N * prow;
+    a.argmax = P<uint8_t>(g.argmax); a.am_env = (long)e.N * 128;
+    chk(by_prec(g.prec_ctrl, mb_ctrl_fwd, mb_ctrl_fwd_f16, mb_ctrl_fwd_x3)(&a, g.num_cu, st), "ctrl_fwd");
   }
 
   void refine(const Cfg& g, u64 S, hipStream_t st) {
+    const mb::EpisodeArgs& e = g.e;
+    RefineCall c = g.r;
+    mb::RefineArgs& r = c.sa.r;
+    r.S = P<const float4>(S);
     mb::CbfFwdArgs a{};
-    a.dim = g.D;
-    a.S = P<const float4>(S); a.s_env = g.Nn; a.s_step = (long)g.B * g.Nn; a.idx = P<const int>(g.idx);
-    a.B = g.B; a.T = 1; a.N = g.N; a.K = g.K; a.two = 0;
-    a.wpack = P<const h16>(g.cbf_w); a.f_fwd = g.f_cbf; a.wvec = P<const float>(g.cbf_v);
-    a.h_out = P<float>(g.h);
-    a.lc = g.lc;
-    a.obs_r = g.obs_r; a.dist_thr = g.dist_thr; a.dist_eps = g.dist_eps;
-    chk((g.prec_cbf == 2 ? mb_cbf_fwd_x3 : mb_cbf_fwd)(&a, g.cbf_blocks, st), "cbf_fwd");
-    mb::CsrArgs r{};
-    r.idx = P<const int>(g.idx); r.G = g.B; r.N = g.N; r.K = g.K; r.Nn = g.Nn;
-    r.ptr = P<int>(g.rptr); r.edges = P<int>(g.redges); r.ws = P<int>(g.csr_ws);
-    chk(mb_rev_csr(&r, st), "rev_csr");
-    const u64 mask = g.mask_done ? g.active : 0;     // validate.py's rule: a finished env is not refined
-    if (g.persistent)
-      chk(refine_small(S, g.Nn, g.D, g.idx, g.A, g.delta, g.h, g.B, g.N, g.Nn, g.K, g.cbf_w, g.f_cbf, g.cbf_rm, g.cbf_v,
-                       g.rptr, g.redges, g.ew, g.loops, g.dt, g.dt_alpha, g.lr, g.obs_r, g.dist_thr, g.dist_eps, 0, 0,
-                       mask, g.prec_cbf, g.stream), "refine_small");
-    else
-      chk(refine_loop(S, g.Nn, g.D, g.idx, g.A, g.delta, g.h, g.B, g.N, g.Nn, g.K, g.cbf_w, g.f_cbf, g.cbf_rm, g.cbf_v,
-                      g.dEv, g.rptr, g.redges, g.ctl, g.loops, g.dt, g.dt_alpha, g.lr, g.obs_r, g.dist_thr, g.dist_eps,
-                      0, 0, mask, g.refine_blocks, g.prec_cbf, g.stream), "refine_loop");
+    a.S = r.S; a.s_env = g.Nn; a.s_step = (long)e.B * g.Nn; a.idx = P<const int>(g.idx);
+    a.B = e.B; a.T = 1; a.N = e.N; a.K = g.K; a.two = 0;
+    a.wpack = r.wpack; a.f_fwd = r.f_bwd; a.wvec = r.wvec;
+    a.h_out = const_cast<float*>(r.h);       // the step's h(s_t) and reverse CSR are written here, read by the filter
+    a.dim = e.dim; a.lc = g.lc;
+    a.obs_r = r.obs_r; a.dist_thr = r.dist_thr; a.dist_eps = r.dist_eps;
+    chk(by_prec(c.prec, mb_cbf_fwd, mb_cbf_fwd_f16, mb_cbf_fwd_x3)(&a, g.cbf_blocks, st), "cbf_fwd");
+    mb::CsrArgs v{};
+    v.idx = P<const int>(g.idx); v.G = e.B; v.N = e.N; v.K = g.K; v.Nn = g.Nn;
+    v.ptr = const_cast<int*>(r.ptr); v.edges = const_cast<int*>(r.edges); v.ws = P<int>(g.csr_ws);
+    chk(mb_rev_csr(&v, st), "rev_csr");
+    if (!g.mask_done) r.env_active = nullptr;        // validate.py's rule: a finished env is not refined
+    if (e.mode == 2) chk(refine_small(&c, st), "refine_small");
+    else chk(refine_loop(&c, st), "refine_loop");
   }
 
   long long* alive_host_ = nullptr;
 };
 
-// The three launches of csrc/episode.hip on their own (which: 0 advance, 1 tally, 2 final), with the
-// arguments EpisodeDriver hands them per step; validated in ops/native.py.
-int episode_kernel(int which, u64 S_cur, u64 S_next, long s_env, int dim, int B, int N, u64 A, u64 delta, u64 G,
-                   float dt, u64 st, u64 dist_fx, u64 safe, u64 active, u64 prev_active, u64 ctl, u64 ew, int loops,
-                   int mode, float thr, u64 out, u64 stream) {
-  mb::EpisodeArgs e{};
-  e.S_cur = P<const float4>(S_cur); e.S_next = P<float4>(S_next); e.s_env = s_env; e.dim = dim; e.B = B; e.N = N;
-  e.A = P<const float>(A); e.delta = P<float>(delta); e.G = P<const float>(G); e.dt = dt;
-  e.st = P<long long>(st); e.dist_fx = P<unsigned long long>(dist_fx); e.safe = P<float>(safe);
-  e.active = P<uint8_t>(active); e.prev_active = P<uint8_t>(prev_active);
-  e.ctl = P<const unsigned long long>(ctl); e.ew = P<unsigned long long>(ew); e.loops = loops; e.mode = mode;
-  e.thr_fx = (unsigned long long)std::llrint((double)thr * (double)N * mb::FX_DIST);
-  e.thr = thr;
-  e.out = P<long long>(out);
-  return which == 0 ? mb_episode_advance(&e, ST(stream)) : which == 1 ? mb_episode_tally(&e, ST(stream))
-                                                                       : mb_episode_final(&e, ST(stream));
-}
-
 }  // namespace
 
 void register_runtime(py::module& m) {
-  m.def("refine_loop", &refine_loop);
-  m.def("refine_small", &refine_small);
-  m.def("episode_kernel", &episode_kernel);
+  def_launch(m, "refine_loop", refine_call, refine_loop);
+  def_launch(m, "refine_small", refine_call, refine_small);
+  // the three launches of csrc/episode.hip on their own, as EpisodeDriver issues them per step
+  def_launch(m, "episode_advance", episode_args, mb_episode_advance);
+  def_launch(m, "episode_tally", episode_args, mb_episode_tally);
+  def_launch(m, "episode_final", episode_args, mb_episode_final);
   py::class_<EpisodeDriver>(m, "EpisodeDriver")
       .def(py::init<>())
       .def("run", &EpisodeDriver::run, py::arg("cfg"));

@@ -75,8 +75,9 @@ def sample_obstacles(B: int, N: int, *, dim: int, num_obstacles: int, points: in
         out = torch.empty(B, M, dim, dtype=torch.float32)
     _chk(out, (B, M, dim), name="obstacles")
     circ, rect, sph = _templates(points)
-    rc = lib().sample_obstacles(out.data_ptr(), B, num_obstacles, points, dim, float(E.side_length(N, dim)),
-                                seed & 0xFFFFFFFFFFFFFFFF, circ.data_ptr(), rect.data_ptr(), sph.data_ptr())
+    rc = lib().sample_obstacles(out=out.data_ptr(), B=B, n_obs=num_obstacles, points=points, dim=dim,
+                                L=float(E.side_length(N, dim)), seed=seed & 0xFFFFFFFFFFFFFFFF,
+                                circle=circ.data_ptr(), rect=rect.data_ptr(), sphere=sph.data_ptr())
     if rc != 0:
         raise ValueError("sample_obstacles: invalid arguments")
     return out
@@ -94,9 +95,10 @@ def sample_scenarios(B: int, N: int, *, dim: int = 2, seed: int = 0, obs: Option
     if obs is not None:
         M = obs.shape[1]
         _chk(obs, (B, M, dim), name="obs")
-    rc = lib().sample_scenarios(S.data_ptr(), G.data_ptr(), obs.data_ptr() if obs is not None else 0, st.data_ptr(),
-                                B, N, dim, M, float(E.side_length(N, dim)), float(r), float(spread),
-                                seed & 0xFFFFFFFFFFFFFFFF, int(max_rounds), int(threads))
+    rc = lib().sample_scenarios(S=S.data_ptr(), G=G.data_ptr(), obs=obs.data_ptr() if obs is not None else 0,
+                                status=st.data_ptr(), B=B, N=N, dim=dim, M=M, L=float(E.side_length(N, dim)), r=float(r),
+                                spread=float(spread), seed=seed & 0xFFFFFFFFFFFFFFFF, max_rounds=int(max_rounds),
+                                threads=int(threads))
     if rc != 0:
         raise ValueError("sample_scenarios: invalid arguments")
     return S, G, st
@@ -107,4 +109,4 @@ def min_pair_distance(p: torch.Tensor, cutoff: float = 1.0) -> float:
     p = p.detach().float().contiguous().cpu()
     n, dim = p.shape
     L = float(p.max().item()) + 1.0 if n else 1.0
-    return float(lib().min_pair_distance(p.data_ptr(), n, dim, dim, L, float(cutoff)))
+    return float(lib().min_pair_distance(p=p.data_ptr(), n=n, dim=dim, stride=dim, L=L, cutoff=float(cutoff)))

@@ -183,6 +183,8 @@ def small_apw(N: int) -> int:
     return max(2, min(32, a + (a & 1)))
 
 
+SCAN_CONSTS = dict(r2_train=float(C.DIST_MIN_THRES * C.DIST_MIN_THRES), ttc_train=float(C.TIME_TO_COLLISION),
+                   r2_check=float(C.DIST_MIN_CHECK * C.DIST_MIN_CHECK), ttc_check=float(C.TIME_TO_COLLISION_CHECK))
 SCAN_MAX_N = 4096           # envs up to this many graph nodes are staged whole in LDS
 SCAN_MAX_NODES = 262144     # beyond SCAN_MAX_N: global staging (csrc/scan.hip scan_stage_kernel); the
                             # culling boxes in LDS up to ~36 K nodes, read from the workspace above
@@ -268,17 +270,16 @@ def scan(S, idx, dang, cnt, safe, *, K, do_knn=True, do_safety=True, perm=None, 
     ws, ws_f4 = scan_ws(B, Nn, S.device)
     if sort:
         L = float(max(1.0, N / C.AGENT_DENSITY) ** (1.0 / D))
-        rc = lib().cell_sort(ptr(S), S.stride(0) // W, B, Nn, L, ptr(perm), W // 4, stream_handle())
+        rc = lib().cell_sort(S=ptr(S), s_env=S.stride(0) // W, B=B, N=Nn, L=L, perm=ptr(perm), rec=W // 4,
+                             stream=stream_handle())
         _ok(rc, "cell_sort")
-    rc = lib().scan(ptr(S), S.stride(0) // W, ptr(perm), B, N, K, ptr(idx) if do_knn else 0,
-                    idx.stride(0) if do_knn else 0, ptr(dang) if do_knn else 0,
-                    ptr(cnt) if do_knn else 0, cnt.stride(0) if (do_knn and cnt is not None) else 0,
-                    ptr(safe) if do_safety else 0, safe.stride(0) if (do_safety and safe is not None) else 0,
-                    float(C.DIST_MIN_THRES * C.DIST_MIN_THRES), float(C.TIME_TO_COLLISION),
-                    float(C.DIST_MIN_CHECK * C.DIST_MIN_CHECK), float(C.TIME_TO_COLLISION_CHECK),
-                    int(do_knn), int(do_safety), Nn, D, ptr(prev_idx),
-                    prev_idx.stride(0) if prev_idx is not None else 0, ptr(ws), int(ws_f4), int(lanes),
-                    ptr(stamps), stream_handle())
+    rc = lib().scan(S=ptr(S), s_env=S.stride(0) // W, perm=ptr(perm), B=B, N=N, K=K, idx=ptr(idx) if do_knn else 0,
+                    i_env=idx.stride(0) if do_knn else 0, dang=ptr(dang) if do_knn else 0,
+                    cnt=ptr(cnt) if do_knn else 0, c_env=cnt.stride(0) if (do_knn and cnt is not None) else 0,
+                    safe=ptr(safe) if do_safety else 0, sf_env=safe.stride(0) if (do_safety and safe is not None) else 0,
+                    do_knn=int(do_knn), do_safety=int(do_safety), Nn=Nn, dim=D, prev_idx=ptr(prev_idx),
+                    pi_env=prev_idx.stride(0) if prev_idx is not None else 0, ws=ptr(ws), ws_env=int(ws_f4),
+                    lanes=int(lanes), stamps=ptr(stamps), stream=stream_handle(), **SCAN_CONSTS)
     _ok(rc, "scan")
 
 
@@ -319,9 +320,10 @@ def scenario(S, G, *, seed, L, r=C.DIST_MIN_THRES, spread=C.GOAL_SPREAD, max_rou
         G1 = max(1, int(_np.floor(_np.float32(span) / _np.float32(r))))
         ws_env = (base + 4 * (G1 + 2) ** D + 255) // 256 * 256      # (+2: float rounding slack)
         ws = _workspace("scenario", B * ws_env, S.device)
-    rc = lib().scenario(ptr(S), S.stride(0) // W, ptr(G), ptr(obs), M, D, B, N, float(L), float(r), float(spread),
-                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds), ptr(status), ptr(ws), int(ws_env),
-                        stream_handle())
+    rc = lib().scenario(S=ptr(S), s_env=S.stride(0) // W, G=ptr(G), obs=ptr(obs), M=M, dim=D, B=B, N=N, L=float(L),
+                        r=float(r), spread=float(spread), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                        max_rounds=int(max_rounds), status=ptr(status), ws=ptr(ws), ws_env=int(ws_env),
+                        stream=stream_handle())
     _ok(rc, "scenario")
 
 
@@ -400,19 +402,19 @@ def ctrl_fwd(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, n
             raise NativeError("ctrl_fwd stamps: int64 buffer of the x3 step")
         if stamps.numel() < 16 * 8 * 2 * num_cu(S.device):       # the grid is at most 2 blocks per CU
             raise NativeError("ctrl_fwd stamps buffer too small")
-    rc = lib().ctrl_fwd(ptr(S), S.stride(0) // W, ptr(G), ptr(idx), idx.stride(0), B, N, K,
-                        ptr(wpack), int(f_edge), int(f_node), ptr(wvec),
-                        ptr(A), A.stride(0) // D if A is not None else 0,
-                        ptr(Sn), Sn.stride(0) // W if Sn is not None else 0,
-                        ptr(dist_sum), dist_sum.stride(0) if dist_sum is not None else 0,
-                        ptr(act_sum), act_sum.stride(0) if act_sum is not None else 0,
-                        ptr(noise), noise.stride(0) // D if noise is not None else 0,
-                        float(C.TIME_STEP), float(C.OBS_RADIUS), float(C.SQRT3),
-                        ptr(pooled), pooled.stride(0) if pooled is not None else 0,
-                        ptr(argmax), argmax.stride(0) if argmax is not None else 0,
-                        D, num_cu(S.device), f16, ctrl_fwd_apw(B * N, S.device, N),
-                        ptr(noise_key), float(noise_prob), float(noise_scale), int(noise_t), ptr(stamps),
-                        stream_handle())
+    rc = lib().ctrl_fwd(S=ptr(S), s_env=S.stride(0) // W, G=ptr(G), idx=ptr(idx), i_env=idx.stride(0), B=B, N=N, K=K,
+                        wpack=ptr(wpack), f_edge=int(f_edge), f_node=int(f_node), wvec=ptr(wvec),
+                        A=ptr(A), a_env=A.stride(0) // D if A is not None else 0,
+                        Snext=ptr(Sn), sn_env=Sn.stride(0) // W if Sn is not None else 0,
+                        dist_sum=ptr(dist_sum), d_env=dist_sum.stride(0) if dist_sum is not None else 0,
+                        act_sum=ptr(act_sum), ac_env=act_sum.stride(0) if act_sum is not None else 0,
+                        noise=ptr(noise), n_env=noise.stride(0) // D if noise is not None else 0,
+                        dt=float(C.TIME_STEP), obs_r=float(C.OBS_RADIUS), sqrt3=float(C.SQRT3),
+                        pooled=ptr(pooled), p_env=pooled.stride(0) if pooled is not None else 0,
+                        argmax=ptr(argmax), am_env=argmax.stride(0) if argmax is not None else 0,
+                        dim=D, num_cu=num_cu(S.device), prec=f16, apw=ctrl_fwd_apw(B * N, S.device, N),
+                        noise_key=ptr(noise_key), noise_prob=float(noise_prob), noise_scale=float(noise_scale),
+                        noise_t=int(noise_t), stamps=ptr(stamps), stream=stream_handle())
     _ok(rc, "ctrl_fwd")
 
 
@@ -438,6 +440,7 @@ def ctrl_fwd_apw(total_agents: int, device, n_agents: int | None = None) -> int:
 
 LOSS_CONSTS = (C.LOSS_EPS_DANG, C.TIME_STEP * C.ALPHA_CBF, C.LOSS_WEIGHTS[0], C.LOSS_WEIGHTS[1],
                C.LOSS_WEIGHTS[2], C.LOSS_WEIGHTS[3], C.LOSS_SCALE)
+CBF_CONSTS = dict(obs_r=float(C.OBS_RADIUS), dist_thr=float(C.DIST_MIN_THRES))      # + dist_eps: per dimension
 
 
 def _loss_consts(grad_scale=1.0, gscale=None):
@@ -488,11 +491,11 @@ def cbf_fwd(S, idx, wpack, f_fwd, wvec, *, dang=None, valid=None, two=True, h_ou
         raise NativeError("packed CBF weights too small")
     nb = num_blocks or cbf_fwd_grid(E, S.device)
     check(partial, torch.float32, (nb, 10), "partial")
-    rc = lib().cbf_fwd(ptr(S), S.stride(1) // W, S.stride(0) // W, ptr(idx), ptr(dang), ptr(valid),
-                       B, T, N, K, int(two), ptr(wpack), int(f_fwd), ptr(wvec), ptr(h_out), ptr(hn_out),
-                       ptr(dh_out), ptr(counts), ptr(partial), LOSS_CONSTS,
-                       float(C.OBS_RADIUS), float(C.DIST_MIN_THRES), float(C.CBF_DIST_EPS_COORD * D), D, nb,
-                       f16, stream_handle())
+    rc = lib().cbf_fwd(S=ptr(S), s_env=S.stride(1) // W, s_step=S.stride(0) // W, idx=ptr(idx), dang=ptr(dang),
+                       valid=ptr(valid), B=B, T=T, N=N, K=K, two=int(two), wpack=ptr(wpack), f_fwd=int(f_fwd),
+                       wvec=ptr(wvec), h_out=ptr(h_out), hn_out=ptr(hn_out), dh_out=ptr(dh_out), counts=ptr(counts),
+                       partial=ptr(partial), lc=LOSS_CONSTS, dim=D, num_blocks=nb, prec=f16, stream=stream_handle(),
+                       dist_eps=float(C.CBF_DIST_EPS_COORD * D), **CBF_CONSTS)
     _ok(rc, "cbf_fwd")
     return nb
 
@@ -530,10 +533,10 @@ def cbf_match(idx, T, map1, src, cnt, *, recomputed=False, nev=None):
     mode = 1 if recomputed else 0
     rowcnt = _workspace("match_rows", rows * 4, idx.device).view(torch.int32)
     # phase 0: match + everything but the extras' offsets; phase 1: the offsets (rows with extras)
-    _ok(lib().cbf_match(ptr(idx), T, B, N, K, mode, 0, ptr(rowcnt), 0, ptr(map1), ptr(src), ptr(cnt), 0,
-                        stream_handle()), "cbf_match/match")
-    _ok(lib().cbf_match(ptr(idx), T, B, N, K, mode, 1, ptr(rowcnt), 0, ptr(map1), ptr(src), ptr(cnt), ptr(nev),
-                        stream_handle()), "cbf_match/extras")
+    kw = dict(idx=ptr(idx), T=T, B=B, N=N, K=K, mode=mode, cnt=ptr(rowcnt), off=0, map1=ptr(map1), src=ptr(src),
+              bsum=ptr(cnt))
+    _ok(lib().cbf_match(phase=0, nev=0, stream=stream_handle(), **kw), "cbf_match/match")
+    _ok(lib().cbf_match(phase=1, nev=ptr(nev), stream=stream_handle(), **kw), "cbf_match/extras")
     return nev
 
 
@@ -581,10 +584,11 @@ def cbf_hfwd(S, idx, idx1, src, nev, wpack, f_fwd, wrm, wvec, h_out, mask_out, n
     if u_end is not None and u_end == u_begin:
         return 0
     nb = num_blocks or cbf_hfwd_grid((u_end if u_end is not None else 2 * E) - u_begin, S.device)
-    rc = lib().cbf_hfwd(ptr(S), S.stride(1) // W, S.stride(0) // W, ptr(idx), ptr(idx1), ptr(src), ptr(nev),
-                        B, T, N, K, ptr(wpack), int(f_fwd), ptr(wrm), ptr(wvec), ptr(h_out), ptr(mask_out),
-                        float(C.OBS_RADIUS), float(C.DIST_MIN_THRES), float(C.CBF_DIST_EPS_COORD * D), D, nb,
-                        f16, int(u_begin), int(u_end or 0), stream_handle())
+    rc = lib().cbf_hfwd(S=ptr(S), s_env=S.stride(1) // W, s_step=S.stride(0) // W, idx=ptr(idx), idx1=ptr(idx1),
+                        src=ptr(src), nev=ptr(nev), B=B, T=T, N=N, K=K, wpack=ptr(wpack), f_fwd=int(f_fwd), wrm=ptr(wrm),
+                        wvec=ptr(wvec), h_out=ptr(h_out), mask_out=ptr(mask_out), dim=D, num_blocks=nb, prec=f16,
+                        u_begin=int(u_begin), u_end=int(u_end or 0), dist_eps=float(C.CBF_DIST_EPS_COORD * D),
+                        stream=stream_handle(), **CBF_CONSTS)
     _ok(rc, "cbf_hfwd")
     return nb
 
@@ -619,9 +623,10 @@ def cbf_dh(h, hmask, map1, src, nev, dang, valid, counts, dh, partial, *, grad_s
     check(partial, torch.float32, None, "partial")
     nb = partial.shape[0]
     check(blk_active, torch.int32, (nb,), "blk_active")
-    _ok(lib().cbf_dh(ptr(h), ptr(hmask), ptr(map1), ptr(src), ptr(nev), ptr(dang), ptr(valid), B, T, N, K,
-                     ptr(counts), _loss_consts(grad_scale, gscale), ptr(dh), ptr(partial),
-                     ptr(blk_active), nb, stream_handle()), "cbf_dh")
+    _ok(lib().cbf_dh(h=ptr(h), hmask=ptr(hmask), map1=ptr(map1), src=ptr(src), nev=ptr(nev), dang=ptr(dang),
+                     valid=ptr(valid), B=B, T=T, N=N, K=K, counts=ptr(counts), lc=_loss_consts(grad_scale, gscale),
+                     dh=ptr(dh), partial=ptr(partial), blk_active=ptr(blk_active), num_blocks=nb,
+                     stream=stream_handle()), "cbf_dh")
 
 
 def cbf_active(dh, nev, blk_active, act, nact=None, *, rec=None, src=None, idx=None, idx1=None):
@@ -649,9 +654,9 @@ def cbf_active(dh, nev, blk_active, act, nact=None, *, rec=None, src=None, idx=N
         nact = torch.empty(1, dtype=torch.int32, device=dh.device)
     check(nact, torch.int32, (1,), "nact")
     E = idx.numel() if idx is not None else 0
-    _ok(lib().cbf_compact(ptr(dh), ptr(nev), 0, ptr(act) if rec is None else 0, blk_active.numel(),
-                          ptr(blk_active), ptr(nact), ptr(src), ptr(idx), ptr(idx1), int(E), ptr(rec),
-                          stream_handle()), "cbf_compact")
+    _ok(lib().cbf_compact(dh=ptr(dh), nev=ptr(nev), blk_off=0, act=ptr(act) if rec is None else 0,
+                          num_blocks=blk_active.numel(), blk_active=ptr(blk_active), nact=ptr(nact), src=ptr(src),
+                          idx=ptr(idx), idx1=ptr(idx1), E=int(E), rec=ptr(rec), stream=stream_handle()), "cbf_compact")
     return nact
 
 
@@ -736,14 +741,15 @@ def cbf_bwd(S, idx, dh, wpack, f_bwd, wrm, wvec, *, passes=2, dE=None, partial=N
     nb = num_blocks or cbf_bwd_grid(E * passes, S.device)
     check(partial, torch.float32, (nb, CBF_PARTIAL), "partial")
     check(stamps, torch.int64, (nb, 8 if (rec is not None or f16 != 2) else 4, 8), "stamps")   # phase cycles
-    rc = lib().cbf_bwd(ptr(S), S.stride(1) // W, S.stride(0) // W, ptr(idx), B, T, N, K, int(passes),
-                       0 if fused else ptr(dh),
-                       ptr(wpack), int(f_bwd), ptr(wrm), ptr(wvec), ptr(dE), ptr(partial), float(C.OBS_RADIUS),
-                       float(C.DIST_MIN_THRES), float(C.CBF_DIST_EPS_COORD * D), int(fused), ptr(dang) if fused else 0,
-                       ptr(valid) if fused else 0, ptr(counts) if fused else 0,
-                       _loss_consts(grad_scale, gscale), ptr(idx1), D, nb,
-                       f16, ptr(src), ptr(nev) if src is not None else 0, ptr(act), ptr(nact) if (act is not None or rec is not None) else 0,
-                       ptr(rec), ptr(wrm16), ptr(w16), ptr(dbg), ptr(stamps), stream_handle())
+    rc = lib().cbf_bwd(S=ptr(S), s_env=S.stride(1) // W, s_step=S.stride(0) // W, idx=ptr(idx), B=B, T=T, N=N, K=K,
+                       passes=int(passes), dh=0 if fused else ptr(dh), wpack=ptr(wpack), f_bwd=int(f_bwd), wrm=ptr(wrm),
+                       wvec=ptr(wvec), dE=ptr(dE), partial=ptr(partial), fused=int(fused), dang=ptr(dang) if fused else 0,
+                       valid=ptr(valid) if fused else 0, counts=ptr(counts) if fused else 0,
+                       lc=_loss_consts(grad_scale, gscale), idx1=ptr(idx1), dim=D, num_blocks=nb, prec=f16, src=ptr(src),
+                       nev=ptr(nev) if src is not None else 0, act=ptr(act),
+                       nact=ptr(nact) if (act is not None or rec is not None) else 0, rec=ptr(rec), wrm16=ptr(wrm16),
+                       w16=ptr(w16), dbg=ptr(dbg), stamps=ptr(stamps), dist_eps=float(C.CBF_DIST_EPS_COORD * D),
+                       stream=stream_handle(), **CBF_CONSTS)
     _ok(rc, "cbf_bwd")
     return nb
 
@@ -759,7 +765,8 @@ def rev_csr(idx, rptr, redges, n_nodes=None):
     ws = None
     if (2 * Nn + 1) * 4 > 150 * 1024:         # counters beyond LDS: csrc/graph.hip global path
         ws = _workspace("csr", Gn * Nn * 4, idx.device)
-    _ok(lib().rev_csr(ptr(idx), Gn, N, K, ptr(rptr), ptr(redges), Nn, ptr(ws), stream_handle()), "rev_csr")
+    _ok(lib().rev_csr(idx=ptr(idx), G=Gn, N=N, K=K, ptr=ptr(rptr), edges=ptr(redges), Nn=Nn, ws=ptr(ws),
+                      stream=stream_handle()), "rev_csr")
 
 
 def node_reduce(dE, rptr, redges, out, *, T, B, N, K, passes=2, accumulate=False, pass_mask=0, shift1=0,
@@ -791,9 +798,10 @@ def node_reduce(dE, rptr, redges, out, *, T, B, N, K, passes=2, accumulate=False
     lo, hi = (0, 0) if t_range is None else (int(t_range[0]), int(t_range[1]))
     if t_range is not None and not (0 <= lo < hi <= T + 1):
         raise NativeError(f"t_range must satisfy 0 <= lo < hi <= T+1 (got {t_range}, T={T})")
-    _ok(lib().node_reduce(ptr(dE), ptr(rptr), ptr(redges), B, T, N, K, passes, int(accumulate), ptr(out),
-                          int(pass_mask), int(shift1), Nn, D, ptr(map1), ptr(gate), int(lo), int(hi),
-                          stream_handle()), "node_reduce")
+    _ok(lib().node_reduce(dE=ptr(dE), ptr=ptr(rptr), edges=ptr(redges), B=B, T=T, N=N, K=K, passes=passes,
+                          accumulate=int(accumulate), out=ptr(out), pass_mask=int(pass_mask), shift1=int(shift1), Nn=Nn,
+                          dim=D, map1=ptr(map1), gate=ptr(gate), t_lo=int(lo), t_hi=int(hi), stream=stream_handle()),
+        "node_reduce")
 
 
 def node_combine(dS_t, ego, dEc, rptr_t, redges_t, Gn, Gout, *, K, dt=C.TIME_STEP):
@@ -810,11 +818,12 @@ def node_combine(dS_t, ego, dEc, rptr_t, redges_t, Gn, Gout, *, K, dt=C.TIME_STE
             raise NativeError("rptr_t must be int32 (B, Nn+1)")
         if redges_t.dtype != torch.int32 or tuple(redges_t.shape) != (B, N * K) or redges_t.stride(1) != 1:
             raise NativeError("redges_t must be int32 (B, N*K)")
-    _ok(lib().node_combine(ptr(dS_t), dS_t.stride(0) // W, ptr(ego), ptr(dEc),
-                           ptr(rptr_t), rptr_t.stride(0) if dEc is not None else 0,
-                           ptr(redges_t), redges_t.stride(0) if dEc is not None else 0,
-                           ptr(Gn), Gn.stride(0) // W if Gn is not None else 0,
-                           ptr(Gout), Gout.stride(0) // W, B, N, K, float(dt), D, stream_handle()), "node_combine")
+    _ok(lib().node_combine(dS=ptr(dS_t), ds_env=dS_t.stride(0) // W, ego=ptr(ego), dEc=ptr(dEc),
+                           ptr=ptr(rptr_t), ptr_env=rptr_t.stride(0) if dEc is not None else 0,
+                           edges=ptr(redges_t), edges_env=redges_t.stride(0) if dEc is not None else 0,
+                           Gn=ptr(Gn), gn_env=Gn.stride(0) // W if Gn is not None else 0, Gout=ptr(Gout),
+                           go_env=Gout.stride(0) // W, B=B, N=N, K=K, dt=float(dt), dim=D, stream=stream_handle()),
+        "node_combine")
 
 
 # ----------------------------------------------------------------------------- safety filter
@@ -830,9 +839,9 @@ def refine_grid(E: int, device, prec_code: int) -> int:
 
 
 def _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec, hn_out, flag_out,
-                 env_active):
+                 env_active, lr):
     """The argument validation shared by ``refine`` and ``refine_small`` ->
-    (B, N, Nn, K, D, loops, precision code, env_active as uint8)."""
+    (B, N, Nn, K, D, loops, precision code, the RefineArgs fields of ``_refine_kw``)."""
     if S is None or S.dim() != 3:
         raise NativeError("S must be (B, Nn, 4|8) node records")
     B, Nn, W = S.shape
@@ -877,7 +886,18 @@ def _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loo
         check(env_active, env_active.dtype, (B,), "env_active")
         if env_active.dtype == torch.bool:
             env_active = env_active.view(torch.uint8)         # same bytes, 0 / 1
-    return B, N, Nn, K, D, loops, code, env_active
+    return B, N, Nn, K, D, loops, code, _refine_kw(B, N, Nn, K, D, S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr,
+                                                   redges, lr, hn_out, flag_out, env_active)
+
+
+def _refine_kw(B, N, Nn, K, D, S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, lr, hn_out=None,
+               flag_out=None, env_active=None, **loop):
+    """The RefineArgs fields (csrc/args.h) both filters take; `loop`: what the caller adds (dEv, ctl, launch parameters)."""
+    return dict(S=ptr(S), s_env=Nn, dim=D, idx=ptr(idx), a=ptr(a), delta=ptr(delta), h=ptr(h), B=B, N=N, Nn=Nn, K=K,
+                wpack=ptr(wpack), f_bwd=int(f_bwd), wrm=ptr(wrm), wvec=ptr(wvec), ptr=ptr(rptr), edges=ptr(redges),
+                dt=float(C.TIME_STEP), dt_alpha=float(C.TIME_STEP * C.ALPHA_CBF), lr=float(lr), hn_out=ptr(hn_out),
+                flag_out=ptr(flag_out), env_active=ptr(env_active), dist_eps=float(C.CBF_DIST_EPS_COORD * D), **CBF_CONSTS,
+                **loop)
 
 
 def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl, *, loops, lr,
@@ -899,8 +919,8 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
     fp32 (x3) and bf16 builds; fp16 is not supported (the -1 upstream gradient has no loss scaling)."""
     if dEv is None or ctl is None:
         raise NativeError("dEv and ctl are required")
-    B, N, Nn, K, D, loops, code, env_active = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges,
-                                                           loops, prec, hn_out, flag_out, env_active)
+    B, N, Nn, K, D, loops, code, kw = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec,
+                                                   hn_out, flag_out, env_active, lr)
     check(dEv, torch.float32, (B, N, K, D), "dEv")
     check(ctl, torch.int64, None, "ctl")
     if ctl.dim() != 1 or ctl.numel() < 2 * loops:
@@ -911,12 +931,8 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
     nb = int(num_blocks) if num_blocks else refine_grid(E, S.device, code)
     if nb < 1 or nb > 4096:
         raise NativeError("num_blocks outside 1..4096")
-    rc = lib().refine_loop(ptr(S), Nn, D, ptr(idx), ptr(a), ptr(delta), ptr(h), B, N, Nn, K, ptr(wpack), int(f_bwd),
-                           ptr(wrm), ptr(wvec), ptr(dEv), ptr(rptr), ptr(redges), ptr(ctl), loops,
-                           float(C.TIME_STEP), float(C.TIME_STEP * C.ALPHA_CBF), float(lr), float(C.OBS_RADIUS),
-                           float(C.DIST_MIN_THRES), float(C.CBF_DIST_EPS_COORD * D), ptr(hn_out), ptr(flag_out),
-                           ptr(env_active), nb, code, stream_handle())
-    _ok(rc, "refine")
+    _ok(lib().refine_loop(loops=loops, num_blocks=nb, prec=code, stream=stream_handle(), dEv=ptr(dEv), ctl=ptr(ctl), **kw),
+        "refine")
     return nb
 
 
@@ -950,15 +966,10 @@ def refine_small(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, ew,
         raise NativeError("loops must be >= 0")
     if ew is None:
         raise NativeError("ew is required")
-    B, N, Nn, K, D, loops, code, env_active = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges,
-                                                           loops, prec, hn_out, flag_out, env_active)
+    B, N, Nn, K, D, loops, code, kw = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec,
+                                                   hn_out, flag_out, env_active, lr)
     check(ew, torch.int64, (B, loops, 2), "ew")
-    rc = lib().refine_small(ptr(S), Nn, D, ptr(idx), ptr(a), ptr(delta), ptr(h), B, N, Nn, K, ptr(wpack), int(f_bwd),
-                            ptr(wrm), ptr(wvec), ptr(rptr), ptr(redges), ptr(ew), loops,
-                            float(C.TIME_STEP), float(C.TIME_STEP * C.ALPHA_CBF), float(lr), float(C.OBS_RADIUS),
-                            float(C.DIST_MIN_THRES), float(C.CBF_DIST_EPS_COORD * D), ptr(hn_out), ptr(flag_out),
-                            ptr(env_active), code, stream_handle())
-    _ok(rc, "refine_small")
+    _ok(lib().refine_small(ew=ptr(ew), loops=loops, prec=code, stream=stream_handle(), **kw), "refine_small")
 
 
 def refine_reduce(ew):
@@ -1040,14 +1051,9 @@ def ctrl_bwd_grids(total_agents: int, device, prec=None, eb16=False):
 NODE16_RM = 64 * 176 + 128 * 80 + 64 * 144 + 16 * 80    # csrc/node16.h: elements per plane (layout.node_rm16)
 
 
-def ctrl_node_bwd(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
-                  act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, _defer=False,
-                  wrm16=None):
-    """act_cnt: optional 1-element device tensor holding the (all-reduced) action-loss count
-    n_act; the action-loss coefficient is then act_coef / max(n_act, 1), read by the kernel (no
-    host round trip, no extra launch). init: write the weight-gradient slabs instead of
-    accumulating into them (no zero fill needed). stamps: diagnostics only, int64
-    (num_blocks, 4, 16) phase clocks of the cooperative 32-agent path (scripts/stamps_node.py)."""
+def _node_bwd_kw(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
+                 act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, wrm16=None):
+    """ctrl_node_bwd's checks -> (the CtrlNodeBwdArgs fields (csrc/args.h) as a dict, precision code)."""
     B, N = G.shape[:2]
     D = dim_of(S)
     W = rec_width(D)
@@ -1069,7 +1075,13 @@ def ctrl_node_bwd(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, e
     check(act_cnt, torch.float32, (1,), "act_cnt")
     check(gscale, torch.float32, (1,), "gscale")
     check(stamps, torch.int64, (num_blocks, 8 if wrm16 is not None else 4, 16), "stamps")
-    cmb = ()
+    kw = dict(pooled=ptr(pooled), p_env=pooled.stride(0), S=ptr(S), s_env=S.stride(0) // W, G=ptr(G), A=ptr(A),
+              a_env=A.stride(0) // D, Gn=ptr(Gn), gn_env=Gn.stride(0) // W if Gn is not None else 0,
+              valid=ptr(valid_t), v_env=valid_t.stride(0) if valid_t is not None else 0, B=B, N=N,
+              wrm=ptr(wrm), o_w1=offs["w1"], o_w2=offs["w2"], o_w3=offs["w3"], o_w4=offs["w4"], wvec=ptr(wvec),
+              act_coef=float(act_coef), act_scale=ptr(act_cnt), dt=float(C.TIME_STEP), sqrt3=float(C.SQRT3), dP=ptr(dP),
+              dp_env=dP.stride(0), ego=ptr(ego), partial=ptr(partial), dim=D, init=int(bool(init)),
+              chunk=int(chunk or node_bwd_chunk(B * N, S.device)), gscale=ptr(gscale), stamps=ptr(stamps))
     if combine is not None:
         # fused BPTT combine: Gn is formed in the kernel from step t+1's records (node_combine's terms)
         c = combine
@@ -1084,32 +1096,34 @@ def ctrl_node_bwd(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, e
         if c["rptr"].dtype != torch.int32 or c["redges"].dtype != torch.int32 or c["rptr"].shape[1] < N + 1:
             raise NativeError("combine rptr / redges must be int32 CSR rows")
         Gn_c = c["Gn"]
-        cmb = (ptr(c["dS"]), c["dS"].stride(0) // W, ptr(c["ego"]), ptr(c["dEc"]), ptr(c["rptr"]), c["rptr"].stride(0),
-               ptr(c["redges"]), c["redges"].stride(0), ptr(Gn_c), Gn_c.stride(0) // W if Gn_c is not None else 0,
-               ptr(c["Gout"]), c["Gout"].stride(0) // W, K)
-    args = (ptr(pooled), pooled.stride(0), ptr(S), S.stride(0) // W, ptr(G), ptr(A), A.stride(0) // D,
-            ptr(Gn), Gn.stride(0) // W if Gn is not None else 0,
-            ptr(valid_t), valid_t.stride(0) if valid_t is not None else 0, B, N,
-            ptr(wrm), offs["w1"], offs["w2"], offs["w3"], offs["w4"], ptr(wvec),
-            float(act_coef), ptr(act_cnt), float(C.TIME_STEP), float(C.SQRT3), ptr(dP), dP.stride(0),
-            ptr(ego), ptr(partial), D, int(num_blocks), f16, int(bool(init)),
-            int(chunk or node_bwd_chunk(B * N, S.device)), ptr(gscale), cmb, ptr(stamps))
-    if _defer:
-        return args
+        kw.update(cdS=ptr(c["dS"]), cds_env=c["dS"].stride(0) // W, cego=ptr(c["ego"]), cdEc=ptr(c["dEc"]),
+                  cptr=ptr(c["rptr"]), cptr_env=c["rptr"].stride(0), cedges=ptr(c["redges"]),
+                  cedges_env=c["redges"].stride(0), cGn=ptr(Gn_c), cgn_env=Gn_c.stride(0) // W if Gn_c is not None else 0,
+                  cGout=ptr(c["Gout"]), cgo_env=c["Gout"].stride(0) // W, K=K)
     if wrm16 is not None:
         # 16x16x32 kernel (csrc/node16.h): 128-agent chunks (eight 16-agent waves)
-        if args[-4] != 128:
+        if kw["chunk"] != 128:
             raise NativeError("16x16x32 node backward: 128-agent chunks only")
         check(wrm16, wrm.dtype, (_planes(f16) * NODE16_RM,), "wrm16")
-    _ok(lib().ctrl_node_bwd(*args, ptr(wrm16), stream_handle()), "ctrl_node_bwd")
+        kw["wrm16"] = ptr(wrm16)
+    return kw, f16
 
 
-def ctrl_edge_bwd(S, idx, argmax, dP, wpack, f_ew1f, f_ew2tn, dEc, partial, num_blocks, prec=None, init=False,
-                  _defer=False, w16=None, stamps=None):
-    """w16 (K = 12): the 16x16x32 fragments (layout.ctrl_edge_packer16) -> the 8-wave 16x16x32 kernel
-    (csrc/ctrl16.h); same slabs, same dEc records. stamps (num_blocks, 8, 16) int64 (diagnostics,
-    16x16x32 kernel): per wave the shader-clock cycles of each loop phase summed over its tiles
-    (slot 15: tiles), scripts/stamps_edge16.py."""
+def ctrl_node_bwd(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
+                  act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, wrm16=None):
+    """act_cnt: optional 1-element device tensor holding the (all-reduced) action-loss count
+    n_act; the action-loss coefficient is then act_coef / max(n_act, 1), read by the kernel (no
+    host round trip, no extra launch). init: write the weight-gradient slabs instead of
+    accumulating into them (no zero fill needed). stamps: diagnostics only, int64
+    (num_blocks, 4, 16) phase clocks of the cooperative 32-agent path (scripts/stamps_node.py)."""
+    kw, f16 = _node_bwd_kw(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
+                           act_cnt, prec, init, chunk, gscale, combine, stamps, wrm16)
+    _ok(lib().ctrl_node_bwd(num_blocks=int(num_blocks), prec=f16, stream=stream_handle(), **kw), "ctrl_node_bwd")
+
+
+def _edge_bwd_kw(S, idx, argmax, dP, wpack, f_ew1f, f_ew2tn, dEc, partial, num_blocks, prec=None, init=False,
+                 w16=None, stamps=None):
+    """ctrl_edge_bwd's checks -> (the CtrlEdgeBwdArgs fields (csrc/args.h) as a dict, precision code)."""
     B, N, K = idx.shape
     D = dim_of(S)
     W = rec_width(D)
@@ -1123,21 +1137,31 @@ def ctrl_edge_bwd(S, idx, argmax, dP, wpack, f_ew1f, f_ew2tn, dEc, partial, num_
         raise NativeError("packed controller weights too small")
     check(dEc, torch.float32, (B, N, K, W), "dEc")
     check(partial, torch.float32, (num_blocks, CTRL_EDGE_PARTIAL), "partial")
-    args = (ptr(S), S.stride(0) // W, ptr(idx), idx.stride(0), ptr(argmax), argmax.stride(0),
-            ptr(dP), dP.stride(0), B, N, K, ptr(wpack), int(f_ew1f), int(f_ew2tn), ptr(dEc),
-            dEc.stride(0) // W if dEc is not None else 0, ptr(partial), D, int(num_blocks),
-            f16, ctrl_edge_qsplit(B * N, S.device), int(bool(init)))
-    if _defer:
-        return args
+    kw = dict(S=ptr(S), s_env=S.stride(0) // W, idx=ptr(idx), i_env=idx.stride(0), argmax=ptr(argmax),
+              am_env=argmax.stride(0), dP=ptr(dP), dp_env=dP.stride(0), B=B, N=N, K=K, wpack=ptr(wpack),
+              f_ew1f=int(f_ew1f), f_ew2tn=int(f_ew2tn), dEc=ptr(dEc), de_env=dEc.stride(0) // W if dEc is not None else 0,
+              partial=ptr(partial), dim=D, qsplit=ctrl_edge_qsplit(B * N, S.device), init=int(bool(init)))
     if w16 is not None:
         if K != 12:
             raise NativeError("16x16x32 edge backward: K = 12 only")
         check(w16, wpack.dtype, (22 * 512 * _planes(f16),), "w16")
+        kw["w16"] = ptr(w16)
     if stamps is not None:
         if w16 is None:
             raise NativeError("edge backward stamps: 16x16x32 kernel only")
         check(stamps, torch.int64, (num_blocks, 8, 16), "stamps")
-    _ok(lib().ctrl_edge_bwd(*args, ptr(w16), ptr(stamps), stream_handle()), "ctrl_edge_bwd")
+        kw["stamps"] = ptr(stamps)
+    return kw, f16
+
+
+def ctrl_edge_bwd(S, idx, argmax, dP, wpack, f_ew1f, f_ew2tn, dEc, partial, num_blocks, prec=None, init=False,
+                  w16=None, stamps=None):
+    """w16 (K = 12): the 16x16x32 fragments (layout.ctrl_edge_packer16) -> the 8-wave 16x16x32 kernel
+    (csrc/ctrl16.h); same slabs, same dEc records. stamps (num_blocks, 8, 16) int64 (diagnostics,
+    16x16x32 kernel): per wave the shader-clock cycles of each loop phase summed over its tiles
+    (slot 15: tiles), scripts/stamps_edge16.py."""
+    kw, f16 = _edge_bwd_kw(S, idx, argmax, dP, wpack, f_ew1f, f_ew2tn, dEc, partial, num_blocks, prec, init, w16, stamps)
+    _ok(lib().ctrl_edge_bwd(num_blocks=int(num_blocks), prec=f16, stream=stream_handle(), **kw), "ctrl_edge_bwd")
 
 
 def ctrl_bwd_step(node: dict, edge: dict, num_blocks: int):
@@ -1145,9 +1169,12 @@ def ctrl_bwd_step(node: dict, edge: dict, num_blocks: int):
     workgroup's 32-agent chunks, then the edge backward of the same agents, in one launch.
     `node` / `edge` are the keyword arguments of ctrl_node_bwd / ctrl_edge_bwd (validated the same
     way); both run on num_blocks workgroups (their slabs need num_blocks rows each)."""
-    na = ctrl_node_bwd(**node, num_blocks=num_blocks, chunk=32, _defer=True)
-    ea = ctrl_edge_bwd(**edge, num_blocks=num_blocks, _defer=True)
-    _ok(lib().ctrl_bwd_step(na, ea, int(num_blocks), na[29], stream_handle()), "ctrl_bwd_step")
+    if node.get("wrm16") is not None or edge.get("w16") is not None or edge.get("stamps") is not None:
+        raise NativeError("ctrl_bwd_step: the fused kernel takes no 16x16x32 images and no edge stamps")
+    na, prec = _node_bwd_kw(**node, num_blocks=num_blocks, chunk=32)
+    ea, _ = _edge_bwd_kw(**edge, num_blocks=num_blocks)
+    _ok(lib().ctrl_bwd_step(node=na, edge=ea, num_blocks=int(num_blocks), prec=prec, stream=stream_handle()),
+        "ctrl_bwd_step")
 
 
 BWD_FUSED_DEFAULT = True
@@ -1169,24 +1196,21 @@ def reduce_multi(jobs):
     (at most 4; the same fixed-order sums as reduce_rows)."""
     if not 1 <= len(jobs) <= 4:
         raise NativeError("reduce_multi takes 1..4 jobs")
-    spec = []
-    for partial, out, acc in jobs:
-        rows, cols = partial.shape
-        check(partial, torch.float32, None, "partial")
-        check(out, torch.float32, (cols,), "out")
-        if cols % 4:
-            raise NativeError("cols must be a multiple of 4")
-        spec.append((ptr(partial), rows, cols, ptr(out), int(bool(acc))))
-    _ok(lib().reduce_multi(spec, stream_handle()), "reduce_multi")
+    _ok(lib().reduce_multi(jobs=[_reduce_job(*j) for j in jobs], stream=stream_handle()), "reduce_multi")
 
 
-def reduce_rows(partial, out, accumulate=False):
+def _reduce_job(partial, out, accumulate):
     rows, cols = partial.shape
     check(partial, torch.float32, None, "partial")
     check(out, torch.float32, (cols,), "out")
     if cols % 4:
         raise NativeError("cols must be a multiple of 4")
-    _ok(lib().reduce_rows(ptr(partial), rows, cols, ptr(out), int(accumulate), stream_handle()), "reduce_rows")
+    return ptr(partial), rows, cols, ptr(out), int(bool(accumulate))
+
+
+def reduce_rows(partial, out, accumulate=False):
+    p, rows, cols, o, acc = _reduce_job(partial, out, accumulate)
+    _ok(lib().reduce_rows(partial=p, rows=rows, cols=cols, out=o, accumulate=acc, stream=stream_handle()), "reduce_rows")
 
 
 FX_DIST = 2.0 ** 32           # csrc/args.h: fixed-point scales of the per-env rollout sums
@@ -1219,8 +1243,9 @@ def rollout_stats(dist, cnt, safe, act, valid, counts, local, *, N, reset=None):
     check(local, torch.float32, None, "local")
     if counts.numel() < 3 or local.numel() < 3:
         raise NativeError("counts / local need 3 slots")
-    _ok(lib().rollout_stats(ptr(dist), ptr(cnt), ptr(safe), ptr(act), T, B, int(N), float(C.DIST_MIN_CHECK),
-                            ptr(valid), ptr(counts), ptr(local), int(reset_T), stream_handle()), "rollout_stats")
+    _ok(lib().rollout_stats(dist=ptr(dist), cnt=ptr(cnt), safe=ptr(safe), act=ptr(act), T=T, B=B, N=int(N),
+                            thr=float(C.DIST_MIN_CHECK), valid=ptr(valid), counts=ptr(counts), local=ptr(local),
+                            reset_T=int(reset_T), stream=stream_handle()), "rollout_stats")
 
 
 def adam_multi(param, grad, m, v, groups, lr, b1, b2, eps, wd, ok=None):
@@ -1237,8 +1262,8 @@ def adam_multi(param, grad, m, v, groups, lr, b1, b2, eps, wd, ok=None):
             raise NativeError("bad Adam range")
         check(sd, torch.int32, (1,), "step_dev")
         spec.append((int(lo), int(hi), ptr(sd)))
-    _ok(lib().adam_multi(ptr(param), ptr(grad), ptr(m), ptr(v), spec, float(b1), float(b2), float(eps), float(wd),
-                         ptr(ok), float(lr), stream_handle()), "adam_multi")
+    _ok(lib().adam_multi(groups=spec, param=ptr(param), grad=ptr(grad), m=ptr(m), v=ptr(v), b1=float(b1), b2=float(b2),
+                         eps=float(eps), wd=float(wd), ok=ptr(ok), lr=float(lr), stream=stream_handle()), "adam_multi")
 
 
 def adam(param, grad, m, v, lo, hi, lr, b1, b2, eps, wd, step, ok=None, step_dev=None):
@@ -1253,9 +1278,9 @@ def adam(param, grad, m, v, lo, hi, lr, b1, b2, eps, wd, step, ok=None, step_dev
     check(step_dev, torch.int32, None, "step_dev")
     bc1 = 1.0 - b1 ** max(step, 1)
     bc2 = 1.0 - b2 ** max(step, 1)
-    _ok(lib().adam(ptr(param), ptr(grad), ptr(m), ptr(v), int(lo), int(hi), float(b1), float(b2), float(eps),
-                   float(wd), float(lr / bc1), float(bc2 ** 0.5), ptr(ok), ptr(step_dev), float(lr),
-                   stream_handle()), "adam")
+    _ok(lib().adam(param=ptr(param), grad=ptr(grad), m=ptr(m), v=ptr(v), lo=int(lo), hi=int(hi), b1=float(b1),
+                   b2=float(b2), eps=float(eps), wd=float(wd), step_size=float(lr / bc1), bc2_sqrt=float(bc2 ** 0.5),
+                   ok=ptr(ok), step=ptr(step_dev), lr=float(lr), stream=stream_handle()), "adam")
 
 
 def pack_gather(src, idx16, out16, idx32, out32, commit=None):
@@ -1269,8 +1294,9 @@ def pack_gather(src, idx16, out16, idx32, out32, commit=None):
     if out16.dtype not in HALF_DTYPES or not out16.is_contiguous() or out16.numel() != idx16.numel():
         raise NativeError("out16 must be a contiguous bf16/fp16 buffer matching idx16")
     n = src.numel()    # index range (<= n + 1) is validated once by ops.weights.PackedWeights
-    _ok(lib().pack_gather(ptr(src), n, ptr(idx16), idx16.numel(), ptr(out16), int(out16.dtype == torch.float16),
-                          ptr(idx32), idx32.numel(), ptr(out32), commit, stream_handle()), "pack_gather")
+    _ok(lib().pack_gather(src=ptr(src), n=n, idx16=ptr(idx16), m16=idx16.numel(), out16=ptr(out16),
+                          f16=int(out16.dtype == torch.float16), idx32=ptr(idx32), m32=idx32.numel(), out32=ptr(out32),
+                          commit=commit, stream=stream_handle()), "pack_gather")
 
 
 def grad_assemble(red, ptr_, src, grad, scale=1.0, gscale=None, ok=None, stats=None):
@@ -1290,8 +1316,9 @@ def grad_assemble(red, ptr_, src, grad, scale=1.0, gscale=None, ok=None, stats=N
     if stats is not None:
         sums, counts, local, row = stats
         _stats_args(sums, counts, local, row)
-    _ok(lib().grad_assemble(ptr(red), ptr(ptr_), ptr(src), n, float(scale), ptr(gscale), ptr(grad), ptr(ok),
-                            ptr(sums), ptr(counts), ptr(local), ptr(row), stream_handle()), "grad_assemble")
+    _ok(lib().grad_assemble(red=ptr(red), ptr=ptr(ptr_), src=ptr(src), n=n, scale=float(scale), gscale=ptr(gscale),
+                            grad=ptr(grad), ok=ptr(ok), sums=ptr(sums), counts=ptr(counts), local=ptr(local), row=ptr(row),
+                            stream=stream_handle()), "grad_assemble")
 
 
 def _stats_args(sums, counts, local, row):
@@ -1309,7 +1336,7 @@ def grad_check(g, ok):
     No host sync."""
     check(g, torch.float32, None, "g")
     check(ok, torch.int32, None, "ok")
-    _ok(lib().grad_check(ptr(g), g.numel(), ptr(ok), stream_handle()), "grad_check")
+    _ok(lib().grad_check(g=ptr(g), n=g.numel(), ok=ptr(ok), stream=stream_handle()), "grad_check")
 
 
 def _check_stats_src(stats_src, stats_row):
@@ -1323,9 +1350,8 @@ def _check_stats_src(stats_src, stats_row):
 
 def step_commit_args(ok, steps, mask, skipped, *, gscale=None, good=None, growth=1000, max_scale=2.0 ** 24,
                      stats_row=None, stats_src=None):
-    """Validated step_commit arguments as the tuple pack_gather(commit=...) takes; stats_src: the
+    """Validated step_commit arguments as the dict pack_gather(commit=...) takes; stats_src: the
     commit first copies stats_row[0:16] from it (the graph-replayed backward's fixed row)."""
-    _check_stats_src(stats_src, stats_row)
     check(ok, torch.int32, (1,), "ok")
     check(steps, torch.int32, None, "steps")
     check(skipped, torch.int32, (1,), "skipped")
@@ -1336,13 +1362,15 @@ def step_commit_args(ok, steps, mask, skipped, *, gscale=None, good=None, growth
     if stats_row is not None and (stats_row.dtype != torch.float32 or stats_row.numel() < 18
                                   or not stats_row.is_contiguous()):
         raise NativeError("stats_row must be a contiguous float32 row of >= 18")
-    return (ptr(ok), ptr(steps), int(mask), steps.numel(), ptr(skipped), ptr(gscale), ptr(good), int(growth),
-            float(max_scale), ptr(stats_row), ptr(stats_src))
+    _check_stats_src(stats_src, stats_row)
+    return dict(ok=ptr(ok), steps=ptr(steps), mask=int(mask), ngroups=steps.numel(), skipped=ptr(skipped),
+                gscale=ptr(gscale), good=ptr(good), growth=int(growth), max_scale=float(max_scale),
+                stats_row=ptr(stats_row), stats_src=ptr(stats_src))
 
 
 def step_commit_raw(args):
-    """step_commit from a step_commit_args tuple (its own launch)."""
-    _ok(lib().step_commit(*args, stream_handle()), "step_commit")
+    """step_commit from a step_commit_args dict (its own launch)."""
+    _ok(lib().step_commit(**args, stream=stream_handle()), "step_commit")
 
 
 def step_commit(ok, steps, mask, skipped, *, gscale=None, good=None, growth=1000, max_scale=2.0 ** 24,
@@ -1350,31 +1378,15 @@ def step_commit(ok, steps, mask, skipped, *, gscale=None, good=None, growth=1000
     """End of an optimizer step on the device: steps[g] += 1 for the groups in mask if *ok, else
     skipped += 1; fp16 (gscale, good): the dynamic loss scale halves on a skipped step and doubles
     after `growth` finite ones; stats_row[16:18] = [skipped, loss scale]; *ok reset to 1."""
-    check(ok, torch.int32, (1,), "ok")
-    check(steps, torch.int32, None, "steps")
-    check(skipped, torch.int32, (1,), "skipped")
-    check(gscale, torch.float32, (1,), "gscale")
-    check(good, torch.int32, (1,), "good")
-    if (gscale is None) != (good is None):
-        raise NativeError("gscale and good go together")
-    if stats_row is not None and (stats_row.dtype != torch.float32 or stats_row.numel() < 18
-                                  or not stats_row.is_contiguous()):
-        raise NativeError("stats_row must be a contiguous float32 row of >= 18")
-    _check_stats_src(stats_src, stats_row)
-    _ok(lib().step_commit(ptr(ok), ptr(steps), int(mask), steps.numel(), ptr(skipped), ptr(gscale), ptr(good),
-                          int(growth), float(max_scale), ptr(stats_row), ptr(stats_src), stream_handle()), "step_commit")
+    step_commit_raw(step_commit_args(ok, steps, mask, skipped, gscale=gscale, good=good, growth=growth,
+                                     max_scale=max_scale, stats_row=stats_row, stats_src=stats_src))
 
 
 def stats_pack(sums, counts, local, row):
     """row[:18] = [sums (10) | counts (3) | local (3) | 0 | 1] (one launch; utils.metrics.StepStats)."""
-    check(sums, torch.float32, None, "sums")
-    check(counts, torch.float32, None, "counts")
-    check(local, torch.float32, None, "local")
-    if sums.numel() < 10 or counts.numel() < 3 or local.numel() < 3:
-        raise NativeError("stats_pack needs 10 sums, 3 counts, 3 local values")
-    if row.dtype != torch.float32 or row.numel() < 18 or not row.is_contiguous():
-        raise NativeError("row must be a contiguous float32 row of >= 18")
-    _ok(lib().stats_pack(ptr(sums), ptr(counts), ptr(local), ptr(row), stream_handle()), "stats_pack")
+    _stats_args(sums, counts, local, row)
+    _ok(lib().stats_pack(sums=ptr(sums), counts=ptr(counts), local=ptr(local), row=ptr(row), stream=stream_handle()),
+        "stats_pack")
 
 
 # ----------------------------------------------------------------------------- closed-loop episodes
@@ -1406,7 +1418,7 @@ def _ep_device(**tensors):
 
 
 def _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active):
-    """The checks shared by the three episode launches -> (B, N, Nn, D)."""
+    """The checks shared by the three episode launches -> (B, N, Nn, D, the EpisodeArgs fields (csrc/args.h) of the state)."""
     if S_cur is None or not isinstance(S_cur, torch.Tensor) or S_cur.dim() != 3:
         raise NativeError("S_cur must be (B, Nn, 4|8) node records")
     B, Nn, W = S_cur.shape
@@ -1425,15 +1437,9 @@ def _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active):
     _ep(safe, torch.float32, (B,), "safe")
     _ep(active, torch.uint8, (B,), "active")
     _ep(prev_active, torch.uint8, (B,), "prev_active")
-    return B, N, Nn, D
-
-
-def _episode_launch(which, S_cur, S_next, N, D, A, delta, G, st, dist_fx, safe, active, prev_active, ctl, ew, loops, mode,
-                    out, what):
-    B, Nn = S_cur.shape[:2]
-    _ok(lib().episode_kernel(which, ptr(S_cur), ptr(S_next), Nn, D, B, N, ptr(A), ptr(delta), ptr(G), float(C.TIME_STEP),
-                             ptr(st), ptr(dist_fx), ptr(safe), ptr(active), ptr(prev_active), ptr(ctl), ptr(ew),
-                             int(loops), int(mode), float(C.DIST_MIN_CHECK), ptr(out), stream_handle()), what)
+    return B, N, Nn, D, dict(s_env=Nn, dim=D, B=B, N=N, A=0, delta=0, G=ptr(G), dt=float(C.TIME_STEP), st=ptr(st),
+                             dist_fx=ptr(dist_fx), safe=ptr(safe), active=ptr(active), prev_active=ptr(prev_active),
+                             ctl=0, ew=0, loops=0, mode=0, thr=float(C.DIST_MIN_CHECK), out=0)
 
 
 def episode_advance(S_cur, S_next, A, delta, G, st, dist_fx, safe, active, prev_active):
@@ -1441,7 +1447,7 @@ def episode_advance(S_cur, S_next, A, delta, G, st, dist_fx, safe, active, prev_
     = s + [v, A + delta] * dt of S_cur's (unchanged when st[0], the "some env still runs" word, is 0),
     dist_fx[b] += sum_i |p'_i - g_i| * FX_DIST. S_cur / S_next (B, Nn, 4|8) distinct record buffers
     (obstacle rows are not touched); A (B, N, D); delta (B, N, D) or None, zeroed once it is read."""
-    B, N, Nn, D = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
+    B, N, Nn, D, kw = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
     _ep(S_next, torch.float32, tuple(S_cur.shape), "S_next")
     _ep(A, torch.float32, (B, N, D), "A")
     _ep(delta, torch.float32, (B, N, D), "delta", required=False)
@@ -1449,8 +1455,8 @@ def episode_advance(S_cur, S_next, A, delta, G, st, dist_fx, safe, active, prev_
         raise NativeError("S_next must not be S_cur")
     _ep_device(S_cur=S_cur, S_next=S_next, A=A, delta=delta, G=G, st=st, dist_fx=dist_fx, safe=safe, active=active,
                prev_active=prev_active)
-    _episode_launch(0, S_cur, S_next, N, D, A, delta, G, st, dist_fx, safe, active, prev_active, None, None, 0, 0, None,
-                    "episode_advance")
+    _ok(lib().episode_advance(S_cur=ptr(S_cur), S_next=ptr(S_next), stream=stream_handle(),
+                              **dict(kw, A=ptr(A), delta=ptr(delta))), "episode_advance")
 
 
 def _episode_words(B, ctl, ew, loops):
@@ -1476,21 +1482,20 @@ def episode_tally(S_cur, G, st, dist_fx, safe, active, prev_active, *, ctl=None,
     filter's iterations], prev_active <- active, active &= dist_fx >= DIST_MIN_CHECK * N, st[0] =
     any(active); dist_fx, safe (and ew) are cleared. ctl: the loop filter's control words; ew
     (B, loops, 2): the persistent filter's; neither: no filter."""
-    B, N, Nn, D = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
+    B, N, Nn, D, kw = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
     loops, mode = _episode_words(B, ctl, ew, loops)
     _ep_device(S_cur=S_cur, G=G, st=st, dist_fx=dist_fx, safe=safe, active=active, prev_active=prev_active, ctl=ctl, ew=ew)
-    _episode_launch(1, S_cur, None, N, D, None, None, G, st, dist_fx, safe, active, prev_active, ctl, ew, loops, mode, None,
-                    "episode_tally")
+    _ok(lib().episode_tally(S_cur=ptr(S_cur), S_next=0, stream=stream_handle(),
+                            **dict(kw, ctl=ptr(ctl), ew=ptr(ew), loops=loops, mode=mode)), "episode_tally")
 
 
 def episode_final(S_cur, G, st, dist_fx, safe, active, prev_active, out):
     """The result vector (episode_final_kernel), after the safety-only scan of the final state S_cur:
     out (EP_OUT,) int64 in the order of validate.COUNTS."""
-    B, N, Nn, D = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
+    B, N, Nn, D, kw = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
     _ep(out, torch.int64, (EP_OUT,), "out")
     _ep_device(S_cur=S_cur, G=G, st=st, dist_fx=dist_fx, safe=safe, active=active, prev_active=prev_active, out=out)
-    _episode_launch(2, S_cur, None, N, D, None, None, G, st, dist_fx, safe, active, prev_active, None, None, 0, 0, out,
-                    "episode_final")
+    _ok(lib().episode_final(S_cur=ptr(S_cur), S_next=0, stream=stream_handle(), **dict(kw, out=ptr(out))), "episode_final")
 
 
 def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask_done, persistent, ctrl, cbf):
@@ -1522,8 +1527,8 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
             raise NativeError("safety filter: fp16 is not supported (the -1 upstream gradient has no loss scaling); "
                               "use fp32 or bf16")
     S0 = buf.get("S0")
-    B, N, Nn, D = _episode_state(S0, buf.get("G"), buf.get("st"), buf.get("dist_fx"), buf.get("safe"),
-                                 buf.get("active"), buf.get("prev_active"))
+    B, N, Nn, D, ep = _episode_state(S0, buf.get("G"), buf.get("st"), buf.get("dist_fx"), buf.get("safe"),
+                                     buf.get("active"), buf.get("prev_active"))
     W = rec_width(D)
     if K > Nn:
         raise NativeError(f"bad K={K} for Nn={Nn}")
@@ -1575,28 +1580,23 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     global _EPISODE_DRIVER
     if _EPISODE_DRIVER is None:
         _EPISODE_DRIVER = lib().EpisodeDriver()
-    cfg = dict(B=B, N=N, Nn=Nn, K=K, D=D, num_cu=num_cu(dev), prec_ctrl=pc, prec_cbf=qc,
+    g = buf.get
+    mode = EP_MODES[None if not filt else "persistent" if persistent else "loop"]
+    ep.update(A=ptr(g("A")), delta=ptr(g("delta") if filt else None), ctl=ptr(g("ctl") if mode == 1 else None),
+              ew=ptr(g("ew") if mode == 2 else None), loops=loops, mode=mode, out=ptr(g("out")))
+    # the filter's arguments (S: per step; the mask is dropped by the driver unless mask_done)
+    flt = _refine_kw(B, N, Nn, K, D, None, g("idx"), g("A"), g("delta"), g("h"), bw, bmp.off["w1f"], brm, bv, g("rptr"),
+                     g("redges"), lr, env_active=g("active"), dEv=ptr(g("dEv") if mode == 1 else None), ctl=ep["ctl"],
+                     ew=ep["ew"], loops=loops, num_blocks=refine_grid(E, dev, qc), prec=qc) if filt else None
+    cfg = dict(episode=ep, refine=flt, Nn=Nn, K=K, num_cu=num_cu(dev), prec_ctrl=pc,
                apw=ctrl_fwd_apw(B * N, dev, N), max_steps=max_steps, check_every=check_every,
-               refine=int(filt), persistent=int(bool(persistent)), loops=loops, mask_done=int(bool(mask_done)),
-               cbf_blocks=cbf_fwd_grid(E, dev) if filt else 0, refine_blocks=refine_grid(E, dev, qc) if filt else 0,
-               f_edge=int(cmp_.off["ew1f"]), f_node=int(cmp_.off["nw1f"]), f_cbf=int(bmp.off["w1f"]) if filt else 0,
-               L=float(max(1.0, N / C.AGENT_DENSITY) ** (1.0 / D)),
-               r2_train=float(C.DIST_MIN_THRES * C.DIST_MIN_THRES), ttc_train=float(C.TIME_TO_COLLISION),
-               r2_check=float(C.DIST_MIN_CHECK * C.DIST_MIN_CHECK), ttc_check=float(C.TIME_TO_COLLISION_CHECK),
-               dt=float(C.TIME_STEP), dt_alpha=float(C.TIME_STEP * C.ALPHA_CBF), lr=float(lr), obs_r=float(C.OBS_RADIUS),
-               sqrt3=float(C.SQRT3), dist_thr=float(C.DIST_MIN_THRES), dist_eps=float(C.CBF_DIST_EPS_COORD * D),
-               done_thr=float(C.DIST_MIN_CHECK), loss_consts=LOSS_CONSTS,
-               S0=ptr(S0), S1=ptr(buf["S1"]), G=ptr(buf["G"]), idx=ptr(buf["idx"]), A=ptr(buf["A"]),
-               pooled=ptr(buf["pooled"]), argmax=ptr(buf["argmax"]), perm=ptr(buf["perm"]), safe=ptr(buf["safe"]),
-               st=ptr(buf["st"]), dist_fx=ptr(buf["dist_fx"]), active=ptr(buf["active"]),
-               prev_active=ptr(buf["prev_active"]), out=ptr(buf["out"]),
-               ctrl_w=ptr(cw), ctrl_v=ptr(cv), cbf_w=ptr(bw) if filt else 0, cbf_rm=ptr(brm) if filt else 0,
-               cbf_v=ptr(bv) if filt else 0, delta=ptr(buf.get("delta")) if filt else 0, h=ptr(buf.get("h")) if filt else 0,
-               rptr=ptr(buf.get("rptr")) if filt else 0, redges=ptr(buf.get("redges")) if filt else 0, csr_ws=ptr(csr_ws),
-               dEv=ptr(buf.get("dEv")) if filt and not persistent else 0,
-               ctl=ptr(buf.get("ctl")) if filt and not persistent else 0,
-               ew=ptr(buf.get("ew")) if filt and persistent else 0,
-               scan_ws=ptr(ws), scan_ws_env=int(ws_f4), stream=stream_handle())
+               mask_done=int(bool(mask_done)), cbf_blocks=cbf_fwd_grid(E, dev) if filt else 0,
+               f_edge=int(cmp_.off["ew1f"]), f_node=int(cmp_.off["nw1f"]),
+               L=float(max(1.0, N / C.AGENT_DENSITY) ** (1.0 / D)), **SCAN_CONSTS,
+               obs_r=float(C.OBS_RADIUS), sqrt3=float(C.SQRT3), loss_consts=LOSS_CONSTS,
+               S0=ptr(S0), S1=ptr(g("S1")), idx=ptr(g("idx")), pooled=ptr(g("pooled")), argmax=ptr(g("argmax")),
+               perm=ptr(g("perm")), ctrl_w=ptr(cw), ctrl_v=ptr(cv), csr_ws=ptr(csr_ws), scan_ws=ptr(ws),
+               scan_ws_env=int(ws_f4), stream=stream_handle())
     try:
         steps, cur = _EPISODE_DRIVER.run(cfg)
     except (RuntimeError, ValueError) as e:
