@@ -63,12 +63,17 @@ class Args {
     else if (PyErr_Occurred()) throw py::error_already_set();
   }
 
-  // a dict-valued argument; with `none`, None is allowed: *none says so and the result holds nothing
-  Args sub(const char* k, bool* none = nullptr) {
+  // a dict-valued argument, read whole by `fill` (every key of it must be asked for); fn: the name its
+  // errors carry. With `none`, None is allowed: *none says so and the result is A{}
+  template <typename A>
+  A sub(const char* k, const char* fn, A (*fill)(Args&), bool* none = nullptr) {
     py::object v = take(k);
-    if (none && (*none = v.is_none())) return Args(fn_, py::dict());
+    if (none && (*none = v.is_none())) return A{};
     if (!py::isinstance<py::dict>(v)) wrong_type(k, "a dict", v);
-    return Args(fn_, py::reinterpret_borrow<py::dict>(v));
+    Args x(fn, py::reinterpret_borrow<py::dict>(v));
+    const A a = fill(x);
+    x.done();
+    return a;
   }
 
   // loss constants (mb::LossConsts): 7 floats (+ optional device loss-scale pointer)

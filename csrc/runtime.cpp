@@ -23,8 +23,7 @@
 #include <tuple>
 #include <vector>
 
-#include "args.h"
-#include "pyargs.h"
+#include "fill.h"
 
 namespace {
 
@@ -32,60 +31,58 @@ hipStream_t ST(u64 s) { return reinterpret_cast<hipStream_t>(static_cast<uintptr
 
 class RolloutDriver {
  public:
-  // (no Args::done() here or in BpttDriver: the engine passes diagnostic keys that not every build reads)
+  // cfg: the driver's own keys and, as dicts, the arguments of its launches at step 0 -- what the
+  // builders of ops/native.py make of the engine's step-0 views (hfwd: of the whole time-major buffers,
+  // None without the overlapped CBF slices). Every key is read before the first HIP call.
   explicit RolloutDriver(py::dict cfg) {
     Args c("RolloutDriver", cfg);
-    c("B", B_); c("N", N_); c("Nn", Nn_); c("K", K_); c("D", D_);
-    W_ = D_ == 2 ? 4 : 8;
-    c("Tmax", Tmax_); c("num_cu", num_cu_); c("prec", prec_); prow_ = prec_ == 2 ? 256 : 128;
-    c("resort_every", resort_); c("compute_safety", safety_); c("overlap_hfwd", overlap_);
-    c("hfwd_blocks", hfwd_blocks_);
-    c("L", L_);
-    c("S", S_); c("G", G_); c("A", A_); c("idx", idx_); c("dang", dang_); c("cnt", cnt_);
-    c("safe", safe_); c("dist", dist_); c("act", act_); c("pooled", pooled_); c("argmax", argmax_);
-    c("perm", perm_); c("host_dist", host_dist_);
-    c("ctrl_w", ctrl_w_); c("f_edge", f_edge_); c("f_node", f_node_); c("ctrl_v", ctrl_v_);
-    c("cbf_w", cbf_w_); c("f_fwd", f_fwd_); c("cbf_rm", cbf_rm_); c("cbf_v", cbf_v_);
-    c("hbuf", hbuf_); c("hmask", hmask_); c("src", src_); c("nev", nev_);
-    c("r2_train", r2_train_); c("ttc_train", ttc_train_); c("r2_check", r2_check_); c("ttc_check", ttc_check_);
-    c("dt", dt_); c("obs_r", obs_r_); c("sqrt3", sqrt3_); c("dist_thr", dist_thr_); c("dist_eps", dist_eps_);
-    c("done_thr", done_thr_);
-    c("check_every", check_);
-    c("noise_key", noise_key_); c("noise_prob", noise_prob_); c("noise_scale", noise_scale_);
-    c("scan_ws", scan_ws_); c("scan_ws_env", scan_ws_env_);
-    c("apw", apw_);
+    c("Tmax", Tmax_); c("resort_every", resort_); c("check_every", check_); c("hfwd_blocks", hfwd_blocks_);
+    c("num_cu", num_cu_); c("prec", prec_); c("host_dist", host_dist_); c("done_thr", done_thr_);
+    // early-stop publication (ctrl.hip publish_step): per-step workgroup counters on the device,
+    // the per-env sums and a flag per step in host-coherent memory
+    c("publish", publish_); c("poll_query_ms", poll_query_ms_);
     c("small_ctl", small_ctl_); c("small_apw", small_apw_); c("knn_tail", knn_tail_);
-    c.opt("small_stamps", small_stamps_);
+    c("small_stamps", small_stamps_);      // diagnostics builds only (else 0)
     // the node MLP's activations per step (T, B*N, node_act_bytes), kept for the cooperative node
     // backward (0 = not kept)
-    c.opt("node_acts", acts_);
-    c.opt("node_act_bytes", act_bytes_);
+    c("node_acts", acts_); c("node_act_bytes", act_bytes_);
+    bool none = false;
+    hfwd_ = c.sub("hfwd", "RolloutDriver hfwd", cbf_hfwd_args, &none);
+    overlap_ = !none;
+    sort_ = c.sub("cell_sort", "RolloutDriver cell_sort", cell_sort_args);
+    scan_ = c.sub("scan", "RolloutDriver scan", scan_args);
+    ctrl_ = c.sub("ctrl", "RolloutDriver ctrl", ctrl_args);
+    c.done();
+    const mb::ScanArgs& s = scan_;
+    const mb::CtrlArgs& a = ctrl_;
+    if (check_ < 1) check_ = 1;
+    if (s.B < 1 || s.N < 1 || s.Nn < s.N || s.K < 1 || s.K > 16 || (s.dim != 2 && s.dim != 3) || Tmax_ < 1 || resort_ < 1 ||
+        a.B != s.B || a.N != s.N || a.K != s.K || a.dim != s.dim || sort_.B != s.B || sort_.N != s.Nn ||
+        (overlap_ && (hfwd_.B != s.B || hfwd_.N != s.N || hfwd_.K != s.K || hfwd_.dim != s.dim)))
+      throw std::invalid_argument("RolloutDriver: bad dimensions");
+    // what the steps offset: all present, on the same records and lists
+    if (!s.S || a.S != s.S || sort_.S != s.S || !s.idx || a.idx != s.idx || !s.dang || !s.cnt || !a.A || !a.Snext ||
+        !a.dist_sum || !a.act_sum || !a.pooled || !a.argmax || !host_dist_)
+      throw std::invalid_argument("RolloutDriver: a required buffer is missing");
     if (small_ctl_) {
       chk(hipHostMalloc((void**)&small_res_, 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
       small_res_[0] = small_res_[1] = 0;
       chk(hipHostGetDevicePointer((void**)&small_res_dev_, small_res_, 0), "hipHostGetDevicePointer");
     }
-    // early-stop publication (ctrl.hip publish_step): per-step workgroup counters on the device,
-    // the per-env sums and a flag per step in host-coherent memory
-    c.opt("publish", publish_);
-    c.opt("poll_query_ms", poll_query_ms_);
     if (publish_) {
-      const size_t nd = (size_t)Tmax_ * B_, bytes = nd * sizeof(unsigned long long) + (size_t)Tmax_ * sizeof(unsigned);
+      const size_t nd = (size_t)Tmax_ * s.B, bytes = nd * sizeof(unsigned long long) + (size_t)Tmax_ * sizeof(unsigned);
       chk(hipHostMalloc((void**)&pub_host_, bytes, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
       std::memset(pub_host_, 0, bytes);
       chk(hipHostGetDevicePointer((void**)&pub_dev_, pub_host_, 0), "hipHostGetDevicePointer");
       chk(hipMalloc((void**)&pub_ctr_, (size_t)Tmax_ * sizeof(unsigned)), "hipMalloc");
       chk(hipMemset(pub_ctr_, 0, (size_t)Tmax_ * sizeof(unsigned)), "hipMemset");   // once: kernels re-arm them
     }
-    if (check_ < 1) check_ = 1;
-    if (B_ < 1|| N_ < 1 || Nn_ < N_ || K_ < 1 || K_ > 16 || (D_ != 2 && D_ != 3) || Tmax_ < 1 || resort_ < 1)
-      throw std::invalid_argument("RolloutDriver: bad dimensions");
     ev_copy_.resize(Tmax_);
     for (auto& e : ev_copy_) chk(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
     // stream -> stream dependencies on one device: a device-scope release is enough (the default
     // system-scope fence writes back / invalidates caches for host visibility and stalls the
     // queue behind it); the copy-completion events the host waits on keep the system fence
-    const unsigned fork_flags = hipEventDisableTiming | (c.i("fork_device_scope") ? hipEventReleaseToDevice : 0u);
+    const unsigned fork_flags = hipEventDisableTiming | hipEventReleaseToDevice;
     chk(hipEventCreateWithFlags(&ev_main_, fork_flags), "hipEventCreate");
     chk(hipEventCreateWithFlags(&ev_side_, fork_flags), "hipEventCreate");
   }
@@ -104,7 +101,8 @@ class RolloutDriver {
   // early-stopped case, where step T's scan ran before the break).
   std::pair<int, bool> run(u64 stream, u64 hstream, u64 copy_stream, bool early_stop) {
     hipStream_t st = ST(stream), hs = ST(hstream), cs = ST(copy_stream);
-    const volatile unsigned long long* hd = P<const volatile unsigned long long>(host_dist_);
+    const volatile unsigned long long* hd = host_dist_;
+    const long B = ctrl_.B;
     int T = Tmax_;
     bool tail = false;
     // published early stop: the controller kernels hand the per-env sums to the host (no marker)
@@ -128,8 +126,8 @@ class RolloutDriver {
       if (early_stop) {
         if (!pub) {
           chk(hipStreamWaitEvent(cs, ev_main_, 0), "hipStreamWaitEvent");
-          chk(hipMemcpyAsync(P<unsigned long long>(host_dist_) + (long)t * B_, P<const unsigned long long>(dist_) + (long)t * B_,
-                             sizeof(unsigned long long) * B_, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
+          chk(hipMemcpyAsync(host_dist_ + t * B, ctrl_.dist_sum + t * B * ctrl_.d_env, sizeof(unsigned long long) * B,
+                             hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
           chk(hipEventRecord(ev_copy_[t], cs), "hipEventRecord");
         }
         // host check every check_every steps (small scenes: a step's kernels take less than
@@ -183,28 +181,17 @@ class RolloutDriver {
   std::tuple<int, bool, bool> run_small(u64 stream, bool early_stop, bool launch_graph, u64 s0, u64 g0) {
     if (!small_ctl_) throw std::runtime_error("RolloutDriver: no small-scene control buffer");
     hipStream_t st = ST(stream);
-    int* ctl = P<int>(small_ctl_);
     mb::RolloutSmallArgs a{};
     mb::CtrlArgs& c = a.c;
-    c.dim = D_;
-    c.S = S_at(0); c.s_env = Nn_;
-    c.G = P<const float>(G_);
-    c.B = B_; c.N = N_; c.K = K_;
-    c.wpack = P<const h16>(ctrl_w_); c.f_edge = f_edge_; c.f_node = f_node_; c.wvec = P<const float>(ctrl_v_);
-    c.A = P<float>(A_);
-    c.dist_sum = P<unsigned long long>(dist_); c.act_sum = P<unsigned long long>(act_);
-    c.noise_key = P<const unsigned long long>(noise_key_); c.noise_prob = noise_prob_; c.noise_scale = noise_scale_;
-    c.dt = dt_; c.obs_r = obs_r_; c.sqrt3 = sqrt3_;
-    c.pooled = P<h16>(pooled_); c.argmax = P<uint8_t>(argmax_);
+    c = ctrl_;          // the time-major bases: the kernel forms each step's views itself
     c.apw = small_apw_;
-    c.stamps = reinterpret_cast<unsigned long long*>(small_stamps_);   // diagnostics builds only (else 0)
-    c.acts = P<unsigned char>(acts_); c.na_env = N_;     // per-step views offset in the kernel
-    a.idx = P<int>(idx_); a.dang = P<uint8_t>(dang_); a.cnt = P<float>(cnt_);
-    a.safe = safety_ ? P<float>(safe_) : nullptr;
-    a.Nn = Nn_; a.Tmax = Tmax_; a.knn_tail = knn_tail_;
-    a.r2_train = r2_train_; a.ttc_train = ttc_train_; a.r2_check = r2_check_; a.ttc_check = ttc_check_;
+    c.stamps = small_stamps_;
+    c.acts = acts_; c.na_env = c.N;
+    a.idx = scan_.idx; a.dang = scan_.dang; a.cnt = scan_.cnt; a.safe = scan_.safe;
+    a.Nn = scan_.Nn; a.Tmax = Tmax_; a.knn_tail = knn_tail_;
+    a.r2_train = scan_.r2_train; a.ttc_train = scan_.ttc_train; a.r2_check = scan_.r2_check; a.ttc_check = scan_.ttc_check;
     a.done_thr = early_stop ? done_thr_ : -INFINITY;
-    a.ctl = ctl;      // zero at allocation; the kernel's last workgroup re-arms it
+    a.ctl = small_ctl_;      // zero at allocation; the kernel's last workgroup re-arms it
     a.res = small_res_dev_;
     a.res_gen = (int)++small_gen_;
     a.s0 = P<const float>(s0); a.g0 = P<const float>(g0);
@@ -247,22 +234,24 @@ class RolloutDriver {
   // hit gives the same T'.
   int first_done(const volatile unsigned long long* hd, int t) const {
     int last = -1;
-    for (int b = 0; b < B_; ++b) {
+    const int B = ctrl_.B;
+    for (int b = 0; b < B; ++b) {
       int q = 0;      // same float arithmetic as rollout_stats_kernel
-      while (q <= t && !((float)((double)hd[(long)q * B_ + b] / mb::FX_DIST) / (float)N_ < done_thr_)) ++q;
+      while (q <= t && !((float)((double)hd[(long)q * B + b] / mb::FX_DIST) / (float)ctrl_.N < done_thr_)) ++q;
       if (q > t) return 0;
       if (q > last) last = q;
     }
     return last + 1;
   }
 
-  const float4* S_at(int t) const { return P<const float4>(S_) + (long)t * B_ * Nn_ * (W_ / 4); }
+  // the per-step views: the step-0 struct with its pointers moved t steps on, each by its own env stride
+  const float4* S_at(int t) const { return sort_.S + (long)t * sort_.B * sort_.s_env * sort_.rec; }
 
   // Waits until the controller kernel of step t has published its per-env sums (flag == this
   // rollout's generation). Polls host-coherent memory; a stream error or a minute without the
   // flag raises instead of spinning forever.
   void wait_published(int t, hipStream_t st) const {
-    const unsigned* flag = reinterpret_cast<const unsigned*>(pub_host_ + (size_t)Tmax_ * B_) + t;
+    const unsigned* flag = reinterpret_cast<const unsigned*>(pub_host_ + (size_t)Tmax_ * ctrl_.B) + t;
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned long n = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != gen_; ++n) {
       if ((n & 4095) == 4095) {
@@ -286,93 +275,65 @@ class RolloutDriver {
 
   void scan_step(int t, hipStream_t st) {
     if (t % resort_ == 0) {
-      mb::CellSortArgs c{};
-      c.S = S_at(t); c.s_env = Nn_; c.B = B_; c.N = Nn_; c.L = L_; c.perm = P<int>(perm_); c.rec = W_ / 4;
+      mb::CellSortArgs c = sort_;
+      c.S = S_at(t);
       chk(mb_cell_sort(&c, st), "cell_sort");
     }
-    mb::ScanArgs a{};
-    a.S = S_at(t); a.s_env = Nn_; a.perm = P<const int>(perm_);
-    a.B = B_; a.N = N_; a.K = K_; a.Nn = Nn_; a.dim = D_;
-    const long nk = (long)N_ * K_;
-    a.idx = P<int>(idx_) + (long)t * B_ * nk; a.i_env = nk;
-    a.dang = P<uint8_t>(dang_) + (long)t * B_ * nk;
-    a.cnt = P<float>(cnt_) + (long)t * B_ * 2; a.c_env = 2;
-    a.safe = safety_ ? P<float>(safe_) + (long)t * B_ : nullptr; a.sf_env = 1;
-    a.r2_train = r2_train_; a.ttc_train = ttc_train_; a.r2_check = r2_check_; a.ttc_check = ttc_check_;
-    a.do_knn = 1; a.do_safety = safety_;
-    a.prev_idx = t > 0 ? P<const int>(idx_) + (long)(t - 1) * B_ * nk : nullptr; a.pi_env = nk;
-    a.ws = P<float4>(scan_ws_); a.ws_env = scan_ws_env_;
+    mb::ScanArgs a = scan_;
+    const long tb = (long)t * a.B;
+    a.S = S_at(t);
+    a.idx += tb * a.i_env; a.dang += tb * a.i_env; a.cnt += tb * a.c_env;
+    if (a.safe) a.safe += tb * a.sf_env;
+    a.prev_idx = t > 0 ? a.idx - a.B * a.i_env : nullptr; a.pi_env = a.i_env;
     chk(mb_scan(&a, st), "scan");
   }
 
   void ctrl_step(int t, hipStream_t st, bool pub = false) {
-    mb::CtrlArgs a{};
+    mb::CtrlArgs a = ctrl_;
+    const long tb = (long)t * a.B;
     if (pub) {
       a.pub_ctr = pub_ctr_ + t;
-      a.pub_dist = pub_dev_ + (long)t * B_;
-      a.pub_flag = reinterpret_cast<unsigned*>(pub_dev_ + (size_t)Tmax_ * B_) + t;
+      a.pub_dist = pub_dev_ + tb;
+      a.pub_flag = reinterpret_cast<unsigned*>(pub_dev_ + (size_t)Tmax_ * a.B) + t;
       a.pub_gen = gen_;
     }
-    a.dim = D_;
-    a.S = S_at(t); a.s_env = Nn_;
-    a.G = P<const float>(G_);
-    const long nk = (long)N_ * K_;
-    a.idx = P<const int>(idx_) + (long)t * B_ * nk; a.i_env = nk;
-    a.acts = acts_ ? P<unsigned char>(acts_) + (long)t * B_ * N_ * act_bytes_ : nullptr; a.na_env = N_;
-    a.B = B_; a.N = N_; a.K = K_;
-    a.wpack = P<const h16>(ctrl_w_); a.f_edge = f_edge_; a.f_node = f_node_; a.wvec = P<const float>(ctrl_v_);
-    a.A = P<float>(A_) + (long)t * B_ * N_ * D_; a.a_env = N_;
-    a.Snext = const_cast<float4*>(S_at(t + 1)); a.sn_env = Nn_;
-    a.dist_sum = P<unsigned long long>(dist_) + (long)t * B_; a.d_env = 1;
-    a.act_sum = P<unsigned long long>(act_) + (long)t * B_; a.ac_env = 1;
-    a.noise = nullptr; a.n_env = 0;
-    a.noise_key = P<const unsigned long long>(noise_key_); a.noise_prob = noise_prob_; a.noise_scale = noise_scale_;
+    a.S = S_at(t); a.Snext += tb * a.sn_env * sort_.rec;
+    a.idx += tb * a.i_env; a.A += tb * a.a_env * a.dim;
+    a.dist_sum += tb * a.d_env; a.act_sum += tb * a.ac_env;
+    a.pooled += tb * a.p_env; a.argmax += tb * a.am_env;
+    a.acts = acts_ ? acts_ + tb * a.N * act_bytes_ : nullptr; a.na_env = a.N;
     a.noise_t = t;
-    a.dt = dt_; a.obs_r = obs_r_; a.sqrt3 = sqrt3_;
-    a.pooled = P<h16>(pooled_) + (long)t * B_ * N_ * prow_; a.p_env = (long)N_ * prow_;
-    a.argmax = P<uint8_t>(argmax_) + (long)t * B_ * N_ * 128; a.am_env = (long)N_ * 128;
-    a.apw = apw_;
     chk(by_prec(prec_, mb_ctrl_fwd, mb_ctrl_fwd_f16, mb_ctrl_fwd_x3)(&a, num_cu_, st), "ctrl_fwd");
   }
 
   // CBF h of the main slots of step t, evaluations [t*BNK, (t+1)*BNK), on the side stream
   void hfwd_slice(int t, hipStream_t hs) {
-    mb::CbfFwdArgs a{};
-    a.dim = D_;
-    const long bnk = (long)B_ * N_ * K_;
-    a.S = P<const float4>(S_); a.s_env = Nn_; a.s_step = (long)B_ * Nn_;
-    a.idx = P<const int>(idx_); a.idx1 = a.idx; a.src = P<const int>(src_); a.nev = P<const int>(nev_);
-    a.B = B_; a.T = t + 1; a.N = N_; a.K = K_; a.two = 1;
-    a.wpack = P<const h16>(cbf_w_); a.f_fwd = f_fwd_; a.wrm = P<const h16>(cbf_rm_);
-    a.wvec = P<const float>(cbf_v_);
-    a.h_out = P<float>(hbuf_); a.mask_out = P<uint8_t>(hmask_);
-    a.obs_r = obs_r_; a.dist_thr = dist_thr_; a.dist_eps = dist_eps_;
-    a.u_begin = (unsigned)(t * bnk); a.u_end = (unsigned)((t + 1) * bnk);
+    mb::CbfFwdArgs a = hfwd_;
+    const long bnk = (long)a.B * a.N * a.K;
+    a.T = t + 1; a.u_begin = (unsigned)(t * bnk); a.u_end = (unsigned)((t + 1) * bnk);
     chk(by_prec(prec_, mb_cbf_hfwd, mb_cbf_hfwd_f16, mb_cbf_hfwd_x3)(&a, hfwd_blocks_, hs), "cbf_hfwd");
   }
 
-  int B_, N_, Nn_, K_, D_, W_, Tmax_, num_cu_, prec_, prow_, resort_, safety_, overlap_, hfwd_blocks_, check_, apw_;
-  int publish_ = 0;
+  mb::CellSortArgs sort_;     // the launches' arguments at step 0
+  mb::ScanArgs scan_;
+  mb::CtrlArgs ctrl_;
+  mb::CbfFwdArgs hfwd_;       // over the whole buffers (overlap_ only)
+  int Tmax_, num_cu_, prec_, resort_, hfwd_blocks_, check_, publish_, poll_query_ms_, small_apw_, knn_tail_;
+  bool overlap_ = false;
+  float done_thr_;
   unsigned gen_ = 0;
-  int poll_query_ms_ = 100;
+  unsigned long long* host_dist_;            // pinned [Tmax][B]: the copied per-env sums
   unsigned long long* pub_host_ = nullptr;   // host view: [Tmax][B] sums, then [Tmax] flags
   unsigned long long* pub_dev_ = nullptr;    // the same memory, device view
   unsigned* pub_ctr_ = nullptr;              // [Tmax] per-step workgroup counters (device)
-  float L_;
-  u64 S_, G_, A_, idx_, dang_, cnt_, safe_, dist_, act_, pooled_, argmax_, perm_, host_dist_;
-  u64 ctrl_w_, ctrl_v_, cbf_w_, cbf_rm_, cbf_v_, hbuf_, hmask_, src_, nev_, noise_key_;
-  float noise_prob_, noise_scale_;
-  u64 scan_ws_;
-  long scan_ws_env_;
-  u64 small_ctl_ = 0, small_stamps_ = 0, acts_ = 0;
-  long act_bytes_ = 0;
-  int small_apw_ = 0, knn_tail_ = 0;
+  int* small_ctl_;
+  unsigned long long* small_stamps_;
+  unsigned char* acts_;
+  long act_bytes_;
   std::vector<u64> bwd_execs_;
   int* small_res_ = nullptr;                 // host-coherent [T, flag] of the persistent rollout
   int* small_res_dev_ = nullptr;             // its device view
   unsigned small_gen_ = 0;
-  int f_edge_, f_node_, f_fwd_;
-  float r2_train_, ttc_train_, r2_check_, ttc_check_, dt_, obs_r_, sqrt3_, dist_thr_, dist_eps_, done_thr_;
   std::vector<hipEvent_t> ev_copy_;
   hipEvent_t ev_main_ = nullptr, ev_side_ = nullptr;
 };
@@ -387,108 +348,86 @@ class RolloutDriver {
 // for small scenes (BASELINE config #2: 32 agents), where Python paid ~15 us per launch.
 class BpttDriver {
  public:
+  // cfg: the driver's own keys and, as the dicts `node` / `edge`, the arguments of ctrl_node_bwd /
+  // ctrl_edge_bwd at step 0 (ops/native.py _node_bwd_kw / _edge_bwd_kw on the engine's step-0 views,
+  // without the fused combine). dS, Gb, rptr, redges: the time-major bases of what the combine reads of
+  // step t+1, which no field of a step-0 struct holds; so Tmax == 1, where no step has a combine, is no
+  // special case. No HIP call here.
   explicit BpttDriver(py::dict cfg) {
     Args c("BpttDriver", cfg);
-    c("B", B_); c("N", N_); c("Nn", Nn_); c("K", K_); c("D", D_);
-    R_ = D_ == 2 ? 1 : 2;
-    c("Tmax", Tmax_); c("prec", prec_); prow_ = prec_ == 2 ? 256 : 128; c("nb_node", nb_node_); c("nb_edge", nb_edge_);
-    c("qsplit", qsplit_);
-    c("pooled", pooled_); c("S", S_); c("G", G_); c("A", A_); c("dS", dS_); c("Gb", Gb_); c("valid", valid_);
-    c("idx", idx_); c("argmax", argmax_); c("rptr", rptr_); c("redges", redges_);
-    c("ctrl_rm", wrm_); c("o_w1", o1_); c("o_w2", o2_); c("o_w3", o3_); c("o_w4", o4_);
-    c("ctrl_v", wvec_); c("act_scale", act_scale_); c("dP", dP_); c("ego", ego_); c("dEc", dEc_);
-    c("part_node", part_node_); c("part_edge", part_edge_);
-    c("ctrl_w", wpack_); c("f_ew1f", f_ew1f_); c("f_ew2tn", f_ew2tn_);
-    c("dt", dt_); c("sqrt3", sqrt3_);
-    c("node_chunk", node_chunk_);
+    c("Tmax", Tmax_); c("prec", prec_); c("nb_node", nb_node_); c("nb_edge", nb_edge_);
     // per-step slab rows (small grids): step t's node / edge workgroups write rows (T-1-t) x grid
     // of the slabs instead of accumulating into one row per workgroup
-    c.opt("step_rows", step_rows_);
-    c.opt("node_acts", acts_);
-    c.opt("node_act_bytes", act_bytes_);
-    c.opt("node_part", node_part_);
-    c.opt("edge_part", edge_part_);
+    c("step_rows", step_rows_); c("node_part", node_part_); c("edge_part", edge_part_);
+    c("fused_step", fused_); c("node_acts", acts_); c("node_act_bytes", act_bytes_);
+    c("dS", dS_); c("Gb", Gb_); c("rptr", rptr_); c("redges", redges_);
+    node_ = c.sub("node", "BpttDriver node", node_bwd_args);
+    edge_ = c.sub("edge", "BpttDriver edge", edge_bwd_args);
+    c.done();
+    const mb::CtrlNodeBwdArgs& n = node_;
+    const mb::CtrlEdgeBwdArgs& e = edge_;
     if (step_rows_ && (node_part_ <= 0 || edge_part_ <= 0))
       throw std::invalid_argument("BpttDriver: step_rows needs the slab row sizes");
-    c.opt("fused_step", fused_);
-    if (fused_ && (node_chunk_ != 32 || nb_node_ != nb_edge_))
+    if (fused_ && (n.chunk != 32 || nb_node_ != nb_edge_ || e.w16))      // (the fused step keeps its own edge phase)
       throw std::invalid_argument("BpttDriver: the fused step needs 32-agent chunks and one grid");
-    c.opt("gscale", gscale_);       // fp16: device loss scale (or 0)
-    c.opt("ctrl_w16", ew16_);       // K = 12: 16x16x32 edge backward fragments
-    c.opt("node_rm16", nw16_);      // 128-agent chunks: 16x16x32 node backward images
-    if (nw16_ && (node_chunk_ != 128 || fused_))
+    if (n.wrm16 && (n.chunk != 128 || fused_))
       throw std::invalid_argument("BpttDriver: the 16x16x32 node backward needs 128-agent chunks");
-    if (B_ < 1 || N_ < 1 || Nn_ < N_ || K_ < 1 || K_ > 16 || (D_ != 2 && D_ != 3) || Tmax_ < 1 || nb_node_ < 1 ||
-        nb_edge_ < 1)
+    if (n.B < 1 || n.N < 1 || n.s_env < n.N || e.K < 1 || e.K > 16 || (n.dim != 2 && n.dim != 3) || Tmax_ < 1 ||
+        nb_node_ < 1 || nb_edge_ < 1 || e.B != n.B || e.N != n.N || e.dim != n.dim || e.S != n.S || e.s_env != n.s_env)
       throw std::invalid_argument("BpttDriver: bad dimensions");
+    if (!n.S || !n.pooled || !n.A || !n.valid || !n.ego || !n.partial || !e.idx || !e.argmax || !e.dEc || !e.partial ||
+        !dS_ || !Gb_ || !rptr_ || !redges_)
+      throw std::invalid_argument("BpttDriver: a required buffer is missing");
   }
 
   // use_acts: this iteration's rollout kept the node activations (RolloutDriver with node_acts)
   void run(int T, float act_coef, u64 stream, bool use_acts) {
     if (T < 1 || T > Tmax_) throw std::invalid_argument("BpttDriver: T out of range");
     hipStream_t st = ST(stream);
-    const long BN = (long)B_ * N_;
-    const long nk = (long)N_ * K_;
+    // strides of the time-major buffers, from the step-0 views: S is contiguous (s_env = Nn nodes)
+    const long B = node_.B, N = node_.N, K = edge_.K, Nn = node_.s_env, R = node_.dim == 2 ? 1 : 2;
+    const long BN = B * N, nk = N * K;
     for (int t = T - 1; t >= 0; --t) {
-      const float4* Gn = P<const float4>(dS_) + (long)T * BN * R_;       // t = T-1: the direct terms dS_T
-      const float4* St = P<const float4>(S_) + (long)t * B_ * Nn_ * R_;
-      mb::CtrlNodeBwdArgs na{};
-      mb::CtrlEdgeBwdArgs ea{};
+      const long tb = t * B;
+      mb::CtrlNodeBwdArgs na = node_;
+      mb::CtrlEdgeBwdArgs ea = edge_;
       {
         mb::CtrlNodeBwdArgs& a = na;
-        a.dim = D_;
-        a.pooled = P<const h16>(pooled_) + (long)t * BN * prow_; a.p_env = (long)N_ * prow_;
-        a.S = St; a.s_env = Nn_;
-        a.G = P<const float>(G_); a.A = P<const float>(A_) + (long)t * BN * D_; a.a_env = N_;
-        a.Gn = Gn; a.gn_env = N_;
-        a.valid = P<const uint8_t>(valid_) + (long)t * B_; a.v_env = 1;
-        a.B = B_; a.N = N_;
-        a.wrm = P<const h16>(wrm_); a.o_w1 = o1_; a.o_w2 = o2_; a.o_w3 = o3_; a.o_w4 = o4_;
-        a.wvec = P<const float>(wvec_); a.act_coef = act_coef; a.act_scale = P<const float>(act_scale_);
-        a.gscale = P<const float>(gscale_);
-        a.dt = dt_; a.sqrt3 = sqrt3_;
-        a.dP = P<h16>(dP_); a.dp_env = (long)N_ * prow_; a.ego = P<float4>(ego_); a.partial = P<float>(part_node_);
+        a.pooled += tb * a.p_env; a.S += tb * a.s_env * R; a.A += tb * a.a_env * a.dim; a.valid += tb * a.v_env;
+        a.Gn = dS_ + T * BN * R;       // t = T-1: the direct terms dS_T
+        a.act_coef = act_coef;
         a.init = t == T - 1;     // the first step of the reverse loop writes the slabs
         if (step_rows_) {
           a.partial += (long)(T - 1 - t) * nb_node_ * node_part_;
           a.init = 1;
         }
-        a.chunk = node_chunk_;
-        a.acts = (use_acts && acts_) ? P<const unsigned char>(acts_) + (long)t * BN * act_bytes_ : nullptr;
-        a.na_env = N_;
-        a.wrm16 = P<const h16>(nw16_);
-        a.K = K_;
+        a.acts = (use_acts && acts_) ? acts_ + tb * N * act_bytes_ : nullptr;
+        a.na_env = N;
+        a.K = K;
         if (t < T - 1) {
           // fused BPTT combine: G_{t+1} from step t+1's records (dS, ego, dEc, graph t+1, G_{t+2})
           const long t1 = t + 1;
-          a.cdS = P<const float4>(dS_) + t1 * BN * R_; a.cds_env = N_;
+          a.cdS = dS_ + t1 * BN * R; a.cds_env = N;
           // dEc is double-buffered by step parity: step t+1's edge records sit in buffer (t+1)&1
           // while step t's edge phase writes buffer t&1 (the fused launch overlaps the two)
-          a.cego = P<const float4>(ego_); a.cdEc = P<const float4>(dEc_) + (t1 & 1) * BN * K_ * R_;
-          a.cptr = P<const int>(rptr_) + t1 * B_ * (Nn_ + 1); a.cptr_env = Nn_ + 1;
-          a.cedges = P<const int>(redges_) + t1 * B_ * nk; a.cedges_env = nk;
-          a.cGn = (t1 == T - 1 ? P<const float4>(dS_) + (long)T * BN * R_ : P<const float4>(Gb_) + (t1 + 1) * BN * R_);
-          a.cgn_env = N_;
-          a.cGout = P<float4>(Gb_) + t1 * BN * R_; a.cgo_env = N_;
+          a.cego = a.ego; a.cdEc = ea.dEc + (t1 & 1) * B * ea.de_env * R;
+          a.cptr = rptr_ + t1 * B * (Nn + 1); a.cptr_env = Nn + 1;
+          a.cedges = redges_ + t1 * B * nk; a.cedges_env = nk;
+          a.cGn = (t1 == T - 1 ? a.Gn : Gb_ + (t1 + 1) * BN * R);
+          a.cgn_env = N;
+          a.cGout = Gb_ + t1 * BN * R; a.cgo_env = N;
         }
       }
       {
         mb::CtrlEdgeBwdArgs& a = ea;
-        a.dim = D_;
-        a.S = St; a.s_env = Nn_;
-        a.idx = P<const int>(idx_) + (long)t * B_ * nk; a.i_env = nk;
-        a.argmax = P<const uint8_t>(argmax_) + (long)t * BN * 128; a.am_env = (long)N_ * 128;
-        a.dP = P<const h16>(dP_); a.dp_env = (long)N_ * prow_;
-        a.B = B_; a.N = N_; a.K = K_;
-        a.wpack = P<const h16>(wpack_); a.f_ew1f = f_ew1f_; a.f_ew2tn = f_ew2tn_;
-        a.dEc = P<float4>(dEc_) + (long)(t & 1) * BN * K_ * R_; a.de_env = nk; a.partial = P<float>(part_edge_);
-        a.qsplit = qsplit_;
+        a.S = na.S;
+        a.idx += tb * a.i_env; a.argmax += tb * a.am_env;
+        a.dEc += (t & 1) * B * a.de_env * R;
         a.init = t == T - 1;
         if (step_rows_) {
           a.partial += (long)(T - 1 - t) * nb_edge_ * edge_part_;
           a.init = 1;
         }
-        a.w16 = fused_ ? nullptr : P<const h16>(ew16_);   // (the fused step keeps its own edge phase)
       }
       if (fused_) {      // node + edge backward of the same 32-agent chunks in one launch
         chk(by_prec(prec_, mb_ctrl_bwd_step, mb_ctrl_bwd_step_f16, mb_ctrl_bwd_step_x3)(&na, &ea, nb_node_, st),
@@ -505,14 +444,15 @@ class BpttDriver {
   }
 
  private:
-  int B_, N_, Nn_, K_, D_, R_, Tmax_, prec_, prow_, nb_node_, nb_edge_, qsplit_, node_chunk_ = 0, fused_ = 0;
-  int step_rows_ = 0;
-  long node_part_ = 0, edge_part_ = 0, act_bytes_ = 0;
-  u64 acts_ = 0;
-  u64 pooled_, S_, G_, A_, dS_, Gb_, valid_, idx_, argmax_, rptr_, redges_, wrm_, wvec_, act_scale_, dP_, ego_, dEc_;
-  u64 part_node_, part_edge_, wpack_, gscale_ = 0, ew16_ = 0, nw16_ = 0;
-  int o1_, o2_, o3_, o4_, f_ew1f_, f_ew2tn_;
-  float dt_, sqrt3_;
+  mb::CtrlNodeBwdArgs node_;      // the launches' arguments at step 0
+  mb::CtrlEdgeBwdArgs edge_;
+  int Tmax_, prec_, nb_node_, nb_edge_, step_rows_, fused_;
+  long node_part_, edge_part_, act_bytes_;
+  const unsigned char* acts_;
+  const float4* dS_;              // (Tmax+1, B, N) direct terms; row T seeds the loop
+  float4* Gb_;                    // (Tmax+1, B, N) G_t out
+  const int* rptr_;               // reverse CSR of every step's graph: (., B, Nn+1) / (., B, N*K)
+  const int* redges_;
 };
 
 // One call of the safety filter: the kernels' arguments (all but r.it) and how they are launched
@@ -616,11 +556,14 @@ class EpisodeDriver {
   struct Cfg {
     mb::EpisodeArgs e;          // all but S_cur / S_next (per step); e.mode != 0: the filter runs
     RefineCall r;               // the filter's, all but S (per step)
-    int Nn, K, num_cu, prec_ctrl, apw, max_steps, check_every, mask_done, cbf_blocks, f_edge, f_node;
-    float L, r2_train, ttc_train, r2_check, ttc_check, obs_r, sqrt3;
-    u64 S0, S1, idx, pooled, argmax, perm, ctrl_w, ctrl_v, csr_ws, scan_ws;
-    long scan_ws_env;
-    mb::LossConsts lc;
+    // the launches' arguments on the first record buffer (S: per step), ops/native.py's builders
+    mb::CellSortArgs sort;
+    mb::ScanArgs scan, scan_final;      // every step's (kNN + safety); the safety-only scan of the final state
+    mb::CtrlArgs ctrl;
+    mb::CbfFwdArgs cbf;         // filter: h(s_t) into r.h
+    mb::CsrArgs csr;            // filter: the reverse CSR into r.ptr / r.edges
+    float4* S1;                 // the second record buffer (the first: scan.S)
+    int num_cu, prec_ctrl, cbf_blocks, max_steps, check_every, mask_done;
     hipStream_t stream;
   };
 
@@ -632,43 +575,50 @@ class EpisodeDriver {
   }
 
  private:
-  // cfg: the driver's own keys, "episode": the EpisodeArgs fields, "refine": the RefineArgs fields or None
+  // cfg: the driver's own keys and one dict per argument struct (refine, cbf, csr: None without the filter)
   static Cfg parse(const py::dict& c) {
     Args x("EpisodeDriver", c);
     Cfg g{};
-    bool none = false;
-    Args ex = x.sub("episode"), rx = x.sub("refine", &none);
-    g.e = episode_args(ex);
-    ex.done();
-    if (!none) g.r = refine_call(rx);
-    rx.done();
-    const mb::EpisodeArgs& e = g.e;
-    const bool filter = e.mode != 0;
-    x("Nn", g.Nn); x("K", g.K); x("num_cu", g.num_cu); x("prec_ctrl", g.prec_ctrl); x("apw", g.apw);
+    bool none = false, no_cbf = false, no_csr = false;
+    g.e = x.sub("episode", "EpisodeDriver episode", episode_args);
+    g.r = x.sub("refine", "EpisodeDriver refine", refine_call, &none);
+    g.sort = x.sub("cell_sort", "EpisodeDriver cell_sort", cell_sort_args);
+    g.scan = x.sub("scan", "EpisodeDriver scan", scan_args);
+    g.scan_final = x.sub("scan_final", "EpisodeDriver scan_final", scan_args);
+    g.ctrl = x.sub("ctrl", "EpisodeDriver ctrl", ctrl_args);
+    g.cbf = x.sub("cbf", "EpisodeDriver cbf", cbf_fwd_args, &no_cbf);
+    g.csr = x.sub("csr", "EpisodeDriver csr", rev_csr_args, &no_csr);
+    x("S1", g.S1); x("num_cu", g.num_cu); x("prec_ctrl", g.prec_ctrl); x("cbf_blocks", g.cbf_blocks);
     x("max_steps", g.max_steps); x("check_every", g.check_every); x("mask_done", g.mask_done);
-    x("cbf_blocks", g.cbf_blocks); x("f_edge", g.f_edge); x("f_node", g.f_node); x("L", g.L);
-    x("r2_train", g.r2_train); x("ttc_train", g.ttc_train); x("r2_check", g.r2_check); x("ttc_check", g.ttc_check);
-    x("obs_r", g.obs_r); x("sqrt3", g.sqrt3); x("S0", g.S0); x("S1", g.S1); x("idx", g.idx); x("pooled", g.pooled);
-    x("argmax", g.argmax); x("perm", g.perm); x("ctrl_w", g.ctrl_w); x("ctrl_v", g.ctrl_v); x("csr_ws", g.csr_ws);
-    x("scan_ws", g.scan_ws); x("scan_ws_env", g.scan_ws_env);
-    g.lc = x.loss_consts<mb::LossConsts>("loss_consts"); g.stream = ST(x.u("stream"));
+    g.stream = ST(x.u("stream"));
     x.done();
-    if (e.B < 1 || e.N < 1 || g.Nn < e.N || e.s_env != g.Nn || g.K < 1 || g.K > 16 || g.K > g.Nn || (e.dim != 2 && e.dim != 3) ||
-        g.max_steps < 0 || e.loops < 0 || e.mode < 0 || e.mode > 2 || g.prec_ctrl < 0 || g.prec_ctrl > 2 || filter == none)
+    const mb::EpisodeArgs& e = g.e;
+    const mb::ScanArgs &s = g.scan, &f = g.scan_final;
+    const mb::CtrlArgs& a = g.ctrl;
+    const bool filter = e.mode != 0;
+    if (e.B < 1 || e.N < 1 || s.Nn < e.N || e.s_env != s.Nn || s.K < 1 || s.K > 16 || s.K > s.Nn || (e.dim != 2 && e.dim != 3) ||
+        g.max_steps < 0 || e.loops < 0 || e.mode < 0 || e.mode > 2 || g.prec_ctrl < 0 || g.prec_ctrl > 2 || filter == none ||
+        no_cbf != none || no_csr != none || s.B != e.B || s.N != e.N || s.dim != e.dim || s.s_env != s.Nn || f.B != e.B ||
+        f.N != e.N || f.Nn != s.Nn || f.dim != e.dim || f.s_env != s.Nn || a.B != e.B || a.N != e.N || a.K != s.K ||
+        a.dim != e.dim || a.s_env != s.Nn || g.sort.B != e.B || g.sort.N != s.Nn || g.sort.s_env != s.Nn)
       throw std::invalid_argument("EpisodeDriver: bad dimensions");
     if (g.check_every < 1) g.check_every = 1;
-    if (!g.S0 || !g.S1 || g.S0 == g.S1 || !e.G || !g.idx || !e.A || !g.argmax || !g.perm || !e.safe || !e.st ||
-        !e.dist_fx || !e.active || !e.prev_active || !e.out || !g.ctrl_w || !g.ctrl_v || (g.prec_ctrl == 2 && !g.pooled))
+    if (!s.S || !g.S1 || s.S == g.S1 || !e.G || !s.idx || a.idx != s.idx || !e.A || a.A != e.A || !a.argmax || !s.perm ||
+        f.perm != s.perm || g.sort.perm != s.perm || !e.safe || s.safe != e.safe || f.safe != e.safe || !e.st || !e.dist_fx ||
+        !e.active || !e.prev_active || !e.out || !a.wpack || !a.wvec || (g.prec_ctrl == 2 && !a.pooled))
       throw std::invalid_argument("EpisodeDriver: a required buffer is missing");
     if (filter) {
       const mb::RefineArgs& r = g.r.sa.r;
       if (g.r.prec == 1) throw std::invalid_argument("EpisodeDriver: the safety filter has no fp16 build");
-      if (r.B != e.B || r.N != e.N || r.Nn != g.Nn || r.K != g.K || r.dim != e.dim || e.loops < 1 ||
-          g.r.sa.loops != e.loops || g.r.sa.ew != e.ew || g.r.prec < 0 || g.r.prec > 2 || r.idx != P<const int>(g.idx))
+      if (r.B != e.B || r.N != e.N || r.Nn != s.Nn || r.K != s.K || r.dim != e.dim || e.loops < 1 ||
+          g.r.sa.loops != e.loops || g.r.sa.ew != e.ew || g.r.prec < 0 || g.r.prec > 2 || r.idx != s.idx ||
+          g.cbf.B != e.B || g.cbf.T != 1 || g.cbf.N != e.N || g.cbf.K != s.K || g.cbf.dim != e.dim || g.cbf.idx != s.idx ||
+          g.csr.G != e.B || g.csr.N != e.N || g.csr.K != s.K || g.csr.Nn != s.Nn || g.csr.idx != s.idx)
         throw std::invalid_argument("EpisodeDriver: bad dimensions");
-      if (!r.wpack || !r.wrm || !r.wvec || !r.delta || r.delta != e.delta || !r.h || !r.ptr || !r.edges || g.cbf_blocks < 1)
+      if (!r.wpack || !r.wrm || !r.wvec || !r.delta || r.delta != e.delta || !r.h || g.cbf.h_out != r.h || !r.ptr ||
+          g.csr.ptr != r.ptr || !r.edges || g.csr.edges != r.edges || !g.cbf.wpack || !g.cbf.wvec || g.cbf_blocks < 1)
         throw std::invalid_argument("EpisodeDriver: a filter buffer is missing");
-      if (e.mode == 2 ? (!e.ew || g.Nn > 64) : (!r.dEv || !r.ctl || g.r.num_blocks < 1))
+      if (e.mode == 2 ? (!e.ew || s.Nn > 64) : (!r.dEv || !r.ctl || g.r.num_blocks < 1))
         throw std::invalid_argument("EpisodeDriver: the filter's result words / workspace are missing");
     }
     return g;
@@ -676,14 +626,16 @@ class EpisodeDriver {
 
   std::pair<int, int> loop(const Cfg& g) {
     hipStream_t st = g.stream;
-    u64 S[2] = {g.S0, g.S1};
+    float4* S[2] = {const_cast<float4*>(g.scan.S), g.S1};
     int cur = 0, t = 0;
     mb::EpisodeArgs e = g.e;
     for (; t < g.max_steps;) {
-      scan(g, S[cur], true, st);
-      ctrl(g, S[cur], st);
+      scan(g, g.scan, S[cur], st);
+      mb::CtrlArgs a = g.ctrl;
+      a.S = S[cur];
+      chk(by_prec(g.prec_ctrl, mb_ctrl_fwd, mb_ctrl_fwd_f16, mb_ctrl_fwd_x3)(&a, g.num_cu, st), "ctrl_fwd");
       if (e.mode) refine(g, S[cur], st);
-      e.S_cur = P<const float4>(S[cur]); e.S_next = P<float4>(S[cur ^ 1]);
+      e.S_cur = S[cur]; e.S_next = S[cur ^ 1];
       chk(mb_episode_advance(&e, st), "episode_advance");
       chk(mb_episode_tally(&e, st), "episode_tally");
       cur ^= 1;
@@ -695,64 +647,28 @@ class EpisodeDriver {
         if (*alive_host_ == 0) break;
       }
     }
-    scan(g, S[cur], false, st);           // the safety count of the final state
-    e.S_cur = P<const float4>(S[cur]); e.S_next = nullptr;
+    scan(g, g.scan_final, S[cur], st);           // the safety count of the final state
+    e.S_cur = S[cur]; e.S_next = nullptr;
     chk(mb_episode_final(&e, st), "episode_final");
     return {t, cur};
   }
 
-  void scan(const Cfg& g, u64 S, bool knn, hipStream_t st) {
-    const mb::EpisodeArgs& e = g.e;
-    const int R = e.dim == 2 ? 1 : 2;
-    mb::CellSortArgs c{};
-    c.S = P<const float4>(S); c.s_env = g.Nn; c.B = e.B; c.N = g.Nn; c.L = g.L; c.perm = P<int>(g.perm); c.rec = R;
+  void scan(const Cfg& g, mb::ScanArgs a, const float4* S, hipStream_t st) {
+    mb::CellSortArgs c = g.sort;
+    c.S = a.S = S;
     chk(mb_cell_sort(&c, st), "cell_sort");
-    mb::ScanArgs a{};
-    a.S = P<const float4>(S); a.s_env = g.Nn; a.perm = P<const int>(g.perm);
-    a.B = e.B; a.N = e.N; a.K = knn ? g.K : 1; a.Nn = g.Nn; a.dim = e.dim;
-    a.idx = knn ? P<int>(g.idx) : nullptr; a.i_env = knn ? (long)e.N * g.K : 0;
-    a.safe = e.safe; a.sf_env = 1;
-    a.r2_train = g.r2_train; a.ttc_train = g.ttc_train; a.r2_check = g.r2_check; a.ttc_check = g.ttc_check;
-    a.do_knn = knn ? 1 : 0; a.do_safety = 1;
-    a.ws = P<float4>(g.scan_ws); a.ws_env = g.scan_ws_env;
     chk(mb_scan(&a, st), "scan");
   }
 
-  void ctrl(const Cfg& g, u64 S, hipStream_t st) {
-    const mb::EpisodeArgs& e = g.e;
-    const int prow = g.prec_ctrl == 2 ? 256 : 128;
-    mb::CtrlArgs a{};
-    a.dim = e.dim; a.apw = g.apw;
-    a.S = P<const float4>(S); a.s_env = g.Nn; a.G = e.G;
-    a.idx = P<const int>(g.idx); a.i_env = (long)e.N * g.K;
-    a.B = e.B; a.N = e.N; a.K = g.K;
-    a.wpack = P<const h16>(g.ctrl_w); a.f_edge = g.f_edge; a.f_node = g.f_node; a.wvec = P<const float>(g.ctrl_v);
-    a.A = const_cast<float*>(e.A); a.a_env = e.N;
-    a.dt = e.dt; a.obs_r = g.obs_r; a.sqrt3 = g.sqrt3;
-    a.pooled = P<h16>(g.pooled); a.p_env = (long)e.N * prow;
-    a.argmax = P<uint8_t>(g.argmax); a.am_env = (long)e.N * 128;
-    chk(by_prec(g.prec_ctrl, mb_ctrl_fwd, mb_ctrl_fwd_f16, mb_ctrl_fwd_x3)(&a, g.num_cu, st), "ctrl_fwd");
-  }
-
-  void refine(const Cfg& g, u64 S, hipStream_t st) {
-    const mb::EpisodeArgs& e = g.e;
+  void refine(const Cfg& g, const float4* S, hipStream_t st) {
     RefineCall c = g.r;
     mb::RefineArgs& r = c.sa.r;
-    r.S = P<const float4>(S);
-    mb::CbfFwdArgs a{};
-    a.S = r.S; a.s_env = g.Nn; a.s_step = (long)e.B * g.Nn; a.idx = P<const int>(g.idx);
-    a.B = e.B; a.T = 1; a.N = e.N; a.K = g.K; a.two = 0;
-    a.wpack = r.wpack; a.f_fwd = r.f_bwd; a.wvec = r.wvec;
-    a.h_out = const_cast<float*>(r.h);       // the step's h(s_t) and reverse CSR are written here, read by the filter
-    a.dim = e.dim; a.lc = g.lc;
-    a.obs_r = r.obs_r; a.dist_thr = r.dist_thr; a.dist_eps = r.dist_eps;
+    mb::CbfFwdArgs a = g.cbf;
+    r.S = a.S = S;         // the step's h(s_t) and reverse CSR are written where the filter reads them
     chk(by_prec(c.prec, mb_cbf_fwd, mb_cbf_fwd_f16, mb_cbf_fwd_x3)(&a, g.cbf_blocks, st), "cbf_fwd");
-    mb::CsrArgs v{};
-    v.idx = P<const int>(g.idx); v.G = e.B; v.N = e.N; v.K = g.K; v.Nn = g.Nn;
-    v.ptr = const_cast<int*>(r.ptr); v.edges = const_cast<int*>(r.edges); v.ws = P<int>(g.csr_ws);
-    chk(mb_rev_csr(&v, st), "rev_csr");
+    chk(mb_rev_csr(&g.csr, st), "rev_csr");
     if (!g.mask_done) r.env_active = nullptr;        // validate.py's rule: a finished env is not refined
-    if (e.mode == 2) chk(refine_small(&c, st), "refine_small");
+    if (g.e.mode == 2) chk(refine_small(&c, st), "refine_small");
     else chk(refine_loop(&c, st), "refine_loop");
   }
 

@@ -355,7 +355,6 @@ class HipEngine:
     def _driver(self):
         """The native rollout driver (csrc/runtime.cpp) over this engine's persistent buffers;
         every pointer it offsets per step is checked here once."""
-        import os
         if self._drv is None:
             cfg = self.tr.cfg
             B, N, Nn, K, D, W, T = self.B, self.N, self.Nn, self.K, self.D, self.W, self.Tmax
@@ -371,47 +370,33 @@ class HipEngine:
             if not self.host_dist.is_pinned() or tuple(self.host_dist.shape) != (T, B):
                 raise native.NativeError("host_dist must be pinned (T, B)")
             pw = self.pw
-            perm = native._perm_buf(B, Nn, self.dev)
             scan_f4 = native.scan_ws_f4(Nn)                          # large envs: global staging
             # owned by the engine (the driver keeps the pointer for its lifetime)
             self._scan_ws = torch.empty(max(B * scan_f4 * 16, 16), dtype=torch.uint8, device=self.dev)
-            scan_ws = self._scan_ws if scan_f4 else None
-            native._perm_sorted.add((B, Nn, str(self.dev)))      # sorted at t = 0 of every run
             overlap = bool(self.dedup and self.overlap_hfwd)
-            BNK = B * N * K
-            c = {k: native.ptr(v[0]) for k, v in exp.items()}
-            c.update(dict(
-                B=B, N=N, Nn=Nn, K=K, D=D, Tmax=T, num_cu=native.num_cu(self.dev), prec=L.PREC_CODE[self.prec],
-                resort_every=int(self.resort_every), compute_safety=int(cfg.compute_safety), overlap_hfwd=int(overlap),
-                hfwd_blocks=native.cbf_hfwd_grid(BNK, self.dev), L=float(max(1.0, N / C.AGENT_DENSITY) ** (1.0 / D)),
-                perm=native.ptr(perm), host_dist=int(self.host_dist.data_ptr()),
-                check_every=int(self.check_every or max(1, min(4, 16384 // (B * N)))),
-                apw=int(native.ctrl_fwd_apw(B * N, self.dev, N)),
-                ctrl_w=native.ptr(pw.ctrl_w), f_edge=int(pw.ctrl_off["ew1f"]), f_node=int(pw.ctrl_off["nw1f"]),
-                ctrl_v=native.ptr(pw.ctrl_v), cbf_w=native.ptr(pw.cbf_w), f_fwd=int(pw.cbf_off["w1f"]),
-                cbf_rm=native.ptr(pw.cbf_rm), cbf_v=native.ptr(pw.cbf_v),
-                hbuf=native.ptr(self.hbuf) if overlap else 0, hmask=native.ptr(self.hmask) if overlap else 0,
-                src=native.ptr(self.src) if overlap else 0, nev=native.ptr(self.nev_host) if overlap else 0,
-                r2_train=float(C.DIST_MIN_THRES * C.DIST_MIN_THRES), ttc_train=float(C.TIME_TO_COLLISION),
-                r2_check=float(C.DIST_MIN_CHECK * C.DIST_MIN_CHECK), ttc_check=float(C.TIME_TO_COLLISION_CHECK),
-                dt=float(C.TIME_STEP), obs_r=float(C.OBS_RADIUS), sqrt3=float(C.SQRT3),
-                dist_thr=float(C.DIST_MIN_THRES), dist_eps=float(C.CBF_DIST_EPS_COORD * D),
-                done_thr=float(C.DIST_MIN_CHECK),
-                noise_key=native.ptr(self.noise_key) if cfg.add_noise_prob > 0 else 0,
-                scan_ws=native.ptr(scan_ws), scan_ws_env=int(scan_f4),
+            # the launches' arguments at step 0, as the Python loop below passes them; the driver moves
+            # the pointers per step (the curve order is made at t = 0 of every run)
+            sort, scan = native._scan_kw(self.S[0], self.idx[0], self.dang[0], self.cnt[0], self.safe[0], K=K,
+                                         do_safety=cfg.compute_safety, n_agents=N,
+                                         ws=(self._scan_ws if scan_f4 else None, scan_f4))
+            ctrl, prec, ncu = native._ctrl_fwd_kw(self.S[0], self.G, self.idx[0], pw.ctrl_w, pw.ctrl_off["ew1f"],
+                                                  pw.ctrl_off["nw1f"], pw.ctrl_v, self.A[0], self.S[1], self.dist[0],
+                                                  self.act[0], **self._noise_args(), pooled=self.pooled[0],
+                                                  argmax=self.argmax[0], prec=self.prec)
+            hfwd = native._cbf_hfwd_kw(self.S, self.idx[:T], self.idx[:T], self.src, self.nev_host, pw.cbf_w,
+                                       pw.cbf_off["w1f"], pw.cbf_rm, pw.cbf_v, self.hbuf, self.hmask,
+                                       prec=self.prec)[0] if overlap else None
+            c = dict(
+                Tmax=T, num_cu=ncu, prec=prec, resort_every=int(self.resort_every),
+                hfwd_blocks=native.cbf_hfwd_grid(B * N * K, self.dev), host_dist=int(self.host_dist.data_ptr()),
+                check_every=int(self.check_every or max(1, min(4, 16384 // (B * N)))), done_thr=float(C.DIST_MIN_CHECK),
                 small_ctl=native.ptr(self.small_ctl) if self.small_rollout else 0,
                 small_apw=int(native.small_apw(N)), knn_tail=int(not self.reuse),
                 small_stamps=native.ptr(self.small_stamps),     # diagnostics builds (scripts/stamps_small.py)
                 node_acts=native.ptr(self.node_acts), node_act_bytes=native.node_act_bytes(self.prec),
-                noise_prob=float(cfg.add_noise_prob), noise_scale=float(cfg.noise_scale),
-                fork_device_scope=1,
                 # early stop published by the controller kernels (no per-step queue marker / copy)
-                publish=knobs.get_int("MACBF_PUBLISH", 1),
-                poll_query_ms=100))
-            if pw.ctrl_v.numel() < 352 or pw.ctrl_w.numel() < (c["f_node"] + 54) * 512 * (2 if pw.x3 else 1):
-                raise native.NativeError("packed controller weights too small")
-            if overlap and (self.hbuf.numel() < 2 * T * BNK or self.src.numel() < 2 * T * BNK):
-                raise native.NativeError("CBF evaluation buffers too small")
+                publish=knobs.get_int("MACBF_PUBLISH", 1), poll_query_ms=100,
+                cell_sort=sort, scan=scan, ctrl=ctrl, hfwd=hfwd)
             self._drv = native.lib().RolloutDriver(c)
         return self._drv
 
@@ -901,23 +886,23 @@ class HipEngine:
             if self.part_node.shape[0] < rows * self.nb_node or self.part_edge.shape[0] < rows * self.nb_edge:
                 raise native.NativeError("controller slab buffers too small")
             pw = self.pw
-            c = {k: native.ptr(v[0]) for k, v in exp.items()}
-            c.update(dict(
-                B=B, N=N, Nn=Nn, K=K, D=D, Tmax=T, prec=L.PREC_CODE[self.prec],
-                nb_node=int(self.nb_node), nb_edge=int(self.nb_edge),
-                qsplit=int(native.ctrl_edge_qsplit(B * N, self.dev)),
-                part_node=native.ptr(self.part_node), part_edge=native.ptr(self.part_edge),
-                ctrl_rm=native.ptr(pw.ctrl_rm), o_w1=int(pw.node_rm_off["w1"]), o_w2=int(pw.node_rm_off["w2"]),
-                o_w3=int(pw.node_rm_off["w3"]), o_w4=int(pw.node_rm_off["w4"]), ctrl_v=native.ptr(pw.ctrl_v),
-                ctrl_w=native.ptr(pw.ctrl_w), f_ew1f=int(pw.ctrl_off["ew1f"]), f_ew2tn=int(pw.ctrl_off["ew2tn"]),
-                dt=float(C.TIME_STEP), sqrt3=float(C.SQRT3),
-                node_chunk=int(native.node_bwd_chunk(B * N, self.dev)),
+            fused = native.bwd_step_fused(B * N, self.dev)
+            # the launches' arguments at step 0, as _bptt_chain passes them (Gn / act_coef: set per run;
+            # the fused combine: per step, from the time-major bases below)
+            node, prec = native._node_bwd_kw(
+                self.pooled[0], self.S[0], self.G, self.A[0], self.dS[0], self.valid_buf[0], pw.ctrl_rm, pw.node_rm_off,
+                pw.ctrl_v, 0.0, self.dP, self.ego, self.part_node[: self.nb_node], self.nb_node, act_cnt=self.counts[2:3],
+                prec=self.prec, gscale=getattr(self.tr, "gscale_dev", None), wrm16=self._node16(B * N))
+            edge, _ = native._edge_bwd_kw(
+                self.S[0], self.idx[0], self.argmax[0], self.dP, pw.ctrl_w, pw.ctrl_off["ew1f"], pw.ctrl_off["ew2tn"],
+                self.dEc[0], self.part_edge[: self.nb_edge], self.nb_edge, prec=self.prec,
+                w16=None if fused else self.eb16_w)
+            c = dict(
+                Tmax=T, prec=prec, nb_node=int(self.nb_node), nb_edge=int(self.nb_edge), fused_step=int(fused),
                 step_rows=int(self.step_rows), node_part=native.CTRL_NODE_PARTIAL, edge_part=native.CTRL_EDGE_PARTIAL,
                 node_acts=native.ptr(self.node_acts), node_act_bytes=native.node_act_bytes(self.prec),
-                fused_step=int(native.bwd_step_fused(B * N, self.dev)),
-                ctrl_w16=native.ptr(self.eb16_w) if self.eb16_w is not None else 0,
-                node_rm16=native.ptr(self._node16(B * N)),
-                gscale=native.ptr(getattr(self.tr, "gscale_dev", None))))
+                dS=native.ptr(self.dS), Gb=native.ptr(self.Gb), rptr=native.ptr(self.rptr),
+                redges=native.ptr(self.redges), node=node, edge=edge)
             self._bdrv = native.lib().BpttDriver(c)
         return self._bdrv
 

@@ -219,19 +219,11 @@ def _perm_buf(B, N, device):
     return t
 
 
-def scan(S, idx, dang, cnt, safe, *, K, do_knn=True, do_safety=True, perm=None, n_agents=None, prev_idx=None,
-         sort=True, lanes=0, stamps=None):
-    """K1 over one timestep. S: (B, N, 4) view with env stride (may be a slice of a (B,T+1,N,4)
-    buffer); idx/dang: (B, N, K) views; cnt: (B, 2) view; safe: (B,) view.
-
-    Two launches: cell_sort orders each env's agents along a Hilbert curve, then the scan walks
-    candidates outward along it (results are order independent; the order only keeps the
-    wave-divergent top-K insertion rare). prev_idx (B, N, K): the previous step's kNN of the same
-    agents; their current distances bound the K-th distance (tighter culling, same result).
-    sort=False reuses the curve order of the previous call on the same perm buffer (the agents
-    moved one step: slightly looser culling, identical results). lanes: lanes per agent (0: by
-    grid size -- 8 when 4-lane 256-thread blocks leave CUs idle; 4 or 8 forces the layout; the
-    lists, bits and counts are identical for either)."""
+def _scan_kw(S, idx, dang, cnt, safe, *, K, do_knn=True, do_safety=True, perm=None, n_agents=None, prev_idx=None,
+             sort=True, lanes=0, stamps=None, ws=None):
+    """scan's checks -> (the CellSortArgs fields (csrc/args.h) as a dict, or None when the curve order of
+    the previous call is reused; the ScanArgs fields). ws: the caller's own (tensor or None, float4s per
+    env) global staging instead of the cached per-stream one (the rollout driver keeps the pointer)."""
     if lanes not in (0, 4, 8):
         raise NativeError("lanes must be 0 (auto), 4 or 8")
     B, Nn = S.shape[0], S.shape[1]
@@ -267,20 +259,38 @@ def scan(S, idx, dang, cnt, safe, *, K, do_knn=True, do_safety=True, perm=None, 
         if not sort and key not in _perm_sorted:
             sort = True
         _perm_sorted.add(key)
-    ws, ws_f4 = scan_ws(B, Nn, S.device)
-    if sort:
-        L = float(max(1.0, N / C.AGENT_DENSITY) ** (1.0 / D))
-        rc = lib().cell_sort(S=ptr(S), s_env=S.stride(0) // W, B=B, N=Nn, L=L, perm=ptr(perm), rec=W // 4,
-                             stream=stream_handle())
-        _ok(rc, "cell_sort")
-    rc = lib().scan(S=ptr(S), s_env=S.stride(0) // W, perm=ptr(perm), B=B, N=N, K=K, idx=ptr(idx) if do_knn else 0,
+    ws, ws_f4 = ws or scan_ws(B, Nn, S.device)
+    if ws_f4 != scan_ws_f4(Nn) or (ws_f4 and ws.numel() < B * ws_f4 * 16):
+        raise NativeError("scan workspace too small")
+    cs = dict(S=ptr(S), s_env=S.stride(0) // W, B=B, N=Nn, L=float(max(1.0, N / C.AGENT_DENSITY) ** (1.0 / D)),
+              perm=ptr(perm), rec=W // 4) if sort else None
+    return cs, dict(S=ptr(S), s_env=S.stride(0) // W, perm=ptr(perm), B=B, N=N, K=K, idx=ptr(idx) if do_knn else 0,
                     i_env=idx.stride(0) if do_knn else 0, dang=ptr(dang) if do_knn else 0,
                     cnt=ptr(cnt) if do_knn else 0, c_env=cnt.stride(0) if (do_knn and cnt is not None) else 0,
                     safe=ptr(safe) if do_safety else 0, sf_env=safe.stride(0) if (do_safety and safe is not None) else 0,
                     do_knn=int(do_knn), do_safety=int(do_safety), Nn=Nn, dim=D, prev_idx=ptr(prev_idx),
                     pi_env=prev_idx.stride(0) if prev_idx is not None else 0, ws=ptr(ws), ws_env=int(ws_f4),
-                    lanes=int(lanes), stamps=ptr(stamps), stream=stream_handle(), **SCAN_CONSTS)
-    _ok(rc, "scan")
+                    lanes=int(lanes), stamps=ptr(stamps), **SCAN_CONSTS)
+
+
+def scan(S, idx, dang, cnt, safe, *, K, do_knn=True, do_safety=True, perm=None, n_agents=None, prev_idx=None,
+         sort=True, lanes=0, stamps=None):
+    """K1 over one timestep. S: (B, N, 4) view with env stride (may be a slice of a (B,T+1,N,4)
+    buffer); idx/dang: (B, N, K) views; cnt: (B, 2) view; safe: (B,) view.
+
+    Two launches: cell_sort orders each env's agents along a Hilbert curve, then the scan walks
+    candidates outward along it (results are order independent; the order only keeps the
+    wave-divergent top-K insertion rare). prev_idx (B, N, K): the previous step's kNN of the same
+    agents; their current distances bound the K-th distance (tighter culling, same result).
+    sort=False reuses the curve order of the previous call on the same perm buffer (the agents
+    moved one step: slightly looser culling, identical results). lanes: lanes per agent (0: by
+    grid size -- 8 when 4-lane 256-thread blocks leave CUs idle; 4 or 8 forces the layout; the
+    lists, bits and counts are identical for either)."""
+    cs, kw = _scan_kw(S, idx, dang, cnt, safe, K=K, do_knn=do_knn, do_safety=do_safety, perm=perm, n_agents=n_agents,
+                      prev_idx=prev_idx, sort=sort, lanes=lanes, stamps=stamps)
+    if cs:
+        _ok(lib().cell_sort(stream=stream_handle(), **cs), "cell_sort")
+    _ok(lib().scan(stream=stream_handle(), **kw), "scan")
 
 
 def scan_plan(B: int, N: int, K: int, *, Nn: int | None = None, dim: int = 2, prev: bool = True, do_knn: bool = True,
@@ -361,12 +371,9 @@ def _records(t, name, lead, W, min_rows=None):
         raise NativeError(f"{name}: expected {lead}x{W} float32 records, got {tuple(t.shape)} {t.stride()}")
 
 
-def ctrl_fwd(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise=None, pooled=None, argmax=None,
-             prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None):
-    """Fused controller step on per-step views: S/Sn (B,Nn,W) node records (agents first),
-    G (B,N,D), idx (B,N,K), A (B,N,D), dist_sum/act_sum (B,) int64 fixed point (x FX_DIST /
-    x FX_ACT: order-independent integer atomics), pooled (B,N,128) bf16
-    ((B,N,256) [hi | lo] rows for prec="fp32", required there), argmax (B,N,128) uint8."""
+def _ctrl_fwd_kw(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise=None, pooled=None, argmax=None,
+                 prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None):
+    """ctrl_fwd's checks -> (the CtrlArgs fields (csrc/args.h) as a dict, precision code, num_cu)."""
     B, N, K = idx.shape
     D = dim_of(S)
     W = rec_width(D)
@@ -402,20 +409,31 @@ def ctrl_fwd(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, n
             raise NativeError("ctrl_fwd stamps: int64 buffer of the x3 step")
         if stamps.numel() < 16 * 8 * 2 * num_cu(S.device):       # the grid is at most 2 blocks per CU
             raise NativeError("ctrl_fwd stamps buffer too small")
-    rc = lib().ctrl_fwd(S=ptr(S), s_env=S.stride(0) // W, G=ptr(G), idx=ptr(idx), i_env=idx.stride(0), B=B, N=N, K=K,
-                        wpack=ptr(wpack), f_edge=int(f_edge), f_node=int(f_node), wvec=ptr(wvec),
-                        A=ptr(A), a_env=A.stride(0) // D if A is not None else 0,
-                        Snext=ptr(Sn), sn_env=Sn.stride(0) // W if Sn is not None else 0,
-                        dist_sum=ptr(dist_sum), d_env=dist_sum.stride(0) if dist_sum is not None else 0,
-                        act_sum=ptr(act_sum), ac_env=act_sum.stride(0) if act_sum is not None else 0,
-                        noise=ptr(noise), n_env=noise.stride(0) // D if noise is not None else 0,
-                        dt=float(C.TIME_STEP), obs_r=float(C.OBS_RADIUS), sqrt3=float(C.SQRT3),
-                        pooled=ptr(pooled), p_env=pooled.stride(0) if pooled is not None else 0,
-                        argmax=ptr(argmax), am_env=argmax.stride(0) if argmax is not None else 0,
-                        dim=D, num_cu=num_cu(S.device), prec=f16, apw=ctrl_fwd_apw(B * N, S.device, N),
-                        noise_key=ptr(noise_key), noise_prob=float(noise_prob), noise_scale=float(noise_scale),
-                        noise_t=int(noise_t), stamps=ptr(stamps), stream=stream_handle())
-    _ok(rc, "ctrl_fwd")
+    kw = dict(S=ptr(S), s_env=S.stride(0) // W, G=ptr(G), idx=ptr(idx), i_env=idx.stride(0), B=B, N=N, K=K,
+              wpack=ptr(wpack), f_edge=int(f_edge), f_node=int(f_node), wvec=ptr(wvec),
+              A=ptr(A), a_env=A.stride(0) // D if A is not None else 0,
+              Snext=ptr(Sn), sn_env=Sn.stride(0) // W if Sn is not None else 0,
+              dist_sum=ptr(dist_sum), d_env=dist_sum.stride(0) if dist_sum is not None else 0,
+              act_sum=ptr(act_sum), ac_env=act_sum.stride(0) if act_sum is not None else 0,
+              noise=ptr(noise), n_env=noise.stride(0) // D if noise is not None else 0,
+              dt=float(C.TIME_STEP), obs_r=float(C.OBS_RADIUS), sqrt3=float(C.SQRT3),
+              pooled=ptr(pooled), p_env=pooled.stride(0) if pooled is not None else 0,
+              argmax=ptr(argmax), am_env=argmax.stride(0) if argmax is not None else 0,
+              dim=D, apw=ctrl_fwd_apw(B * N, S.device, N),
+              noise_key=ptr(noise_key), noise_prob=float(noise_prob), noise_scale=float(noise_scale),
+              noise_t=int(noise_t), stamps=ptr(stamps))
+    return kw, f16, num_cu(S.device)
+
+
+def ctrl_fwd(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise=None, pooled=None, argmax=None,
+             prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None):
+    """Fused controller step on per-step views: S/Sn (B,Nn,W) node records (agents first),
+    G (B,N,D), idx (B,N,K), A (B,N,D), dist_sum/act_sum (B,) int64 fixed point (x FX_DIST /
+    x FX_ACT: order-independent integer atomics), pooled (B,N,128) bf16
+    ((B,N,256) [hi | lo] rows for prec="fp32", required there), argmax (B,N,128) uint8."""
+    kw, f16, ncu = _ctrl_fwd_kw(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise, pooled, argmax,
+                                prec, noise_key, noise_prob, noise_scale, noise_t, stamps)
+    _ok(lib().ctrl_fwd(num_cu=ncu, prec=f16, stream=stream_handle(), **kw), "ctrl_fwd")
 
 
 def ctrl_fwd_apw(total_agents: int, device, n_agents: int | None = None) -> int:
@@ -470,9 +488,9 @@ def _time_major_S(S, T, B, N, need):
     return dim_of(S), W
 
 
-def cbf_fwd(S, idx, wpack, f_fwd, wvec, *, dang=None, valid=None, two=True, h_out=None, hn_out=None,
-            dh_out=None, counts=None, partial=None, num_blocks=None, prec=None):
-    """Time-major: S (>=T+two, B, N, 4); idx/dang/h (T, B, N, K); valid (T, B); dh (2, T, B, N, K)."""
+def _cbf_fwd_kw(S, idx, wpack, f_fwd, wvec, *, dang=None, valid=None, two=True, h_out=None, hn_out=None,
+                dh_out=None, counts=None, partial=None, num_blocks=None, prec=None):
+    """cbf_fwd's checks -> (the CbfFwdArgs fields (csrc/args.h) as a dict, precision code, num_blocks)."""
     T, B, N, K = idx.shape
     check(idx, torch.int32, None, "idx")
     D, W = _time_major_S(S, T, B, N, 1 if two else 0)
@@ -491,12 +509,19 @@ def cbf_fwd(S, idx, wpack, f_fwd, wvec, *, dang=None, valid=None, two=True, h_ou
         raise NativeError("packed CBF weights too small")
     nb = num_blocks or cbf_fwd_grid(E, S.device)
     check(partial, torch.float32, (nb, 10), "partial")
-    rc = lib().cbf_fwd(S=ptr(S), s_env=S.stride(1) // W, s_step=S.stride(0) // W, idx=ptr(idx), dang=ptr(dang),
-                       valid=ptr(valid), B=B, T=T, N=N, K=K, two=int(two), wpack=ptr(wpack), f_fwd=int(f_fwd),
-                       wvec=ptr(wvec), h_out=ptr(h_out), hn_out=ptr(hn_out), dh_out=ptr(dh_out), counts=ptr(counts),
-                       partial=ptr(partial), lc=LOSS_CONSTS, dim=D, num_blocks=nb, prec=f16, stream=stream_handle(),
-                       dist_eps=float(C.CBF_DIST_EPS_COORD * D), **CBF_CONSTS)
-    _ok(rc, "cbf_fwd")
+    kw = dict(S=ptr(S), s_env=S.stride(1) // W, s_step=S.stride(0) // W, idx=ptr(idx), dang=ptr(dang),
+              valid=ptr(valid), B=B, T=T, N=N, K=K, two=int(two), wpack=ptr(wpack), f_fwd=int(f_fwd),
+              wvec=ptr(wvec), h_out=ptr(h_out), hn_out=ptr(hn_out), dh_out=ptr(dh_out), counts=ptr(counts),
+              partial=ptr(partial), lc=LOSS_CONSTS, dim=D, dist_eps=float(C.CBF_DIST_EPS_COORD * D), **CBF_CONSTS)
+    return kw, f16, nb
+
+
+def cbf_fwd(S, idx, wpack, f_fwd, wvec, *, dang=None, valid=None, two=True, h_out=None, hn_out=None,
+            dh_out=None, counts=None, partial=None, num_blocks=None, prec=None):
+    """Time-major: S (>=T+two, B, N, 4); idx/dang/h (T, B, N, K); valid (T, B); dh (2, T, B, N, K)."""
+    kw, f16, nb = _cbf_fwd_kw(S, idx, wpack, f_fwd, wvec, dang=dang, valid=valid, two=two, h_out=h_out, hn_out=hn_out,
+                              dh_out=dh_out, counts=counts, partial=partial, num_blocks=num_blocks, prec=prec)
+    _ok(lib().cbf_fwd(num_blocks=nb, prec=f16, stream=stream_handle(), **kw), "cbf_fwd")
     return nb
 
 
@@ -551,14 +576,10 @@ def cbf_hfwd_grid(EV: int, device, per_cu: int | None = None) -> int:
     return max(1, min((tiles + HFWD_WAVES - 1) // HFWD_WAVES, num_cu(device) * per_cu))
 
 
-def cbf_hfwd(S, idx, idx1, src, nev, wpack, f_fwd, wrm, wvec, h_out, mask_out, num_blocks=None,
-             u_begin=0, u_end=None, prec=None):
-    """h (masked) and the radius mask of every evaluation u_begin <= u < (u_end or nev) of the
-    deduplicated list: S (>= T+1, B, N, W); idx / idx1 (T, B, N, K) (idx1 = idx for
-    reuse_nbr_idx); src, h_out, mask_out (>= 2E,). Weights: w1f fragments at f_fwd of wpack + the
-    row-major W2|W3 image. A host range [u_begin, u_end) within the main slots (u_end <= E) needs
-    neither src nor nev contents: the rollout evaluates step t's main slots (idx[:t+1]) while
-    later steps are still being simulated."""
+def _cbf_hfwd_kw(S, idx, idx1, src, nev, wpack, f_fwd, wrm, wvec, h_out, mask_out, num_blocks=None,
+                 u_begin=0, u_end=None, prec=None):
+    """cbf_hfwd's checks -> (the CbfFwdArgs fields (csrc/args.h) as a dict, precision code, num_blocks: 0
+    for an empty host range, which launches nothing)."""
     T, B, N, K = idx.shape
     check(idx, torch.int32, None, "idx")
     check(idx1, torch.int32, (T, B, N, K), "idx1")
@@ -581,15 +602,26 @@ def cbf_hfwd(S, idx, idx1, src, nev, wpack, f_fwd, wrm, wvec, h_out, mask_out, n
     check(wvec, torch.float32, None, "wvec")
     if wpack.numel() < (f_fwd + 2) * 512 * _planes(f16):
         raise NativeError("packed CBF weights too small")
-    if u_end is not None and u_end == u_begin:
-        return 0
     nb = num_blocks or cbf_hfwd_grid((u_end if u_end is not None else 2 * E) - u_begin, S.device)
-    rc = lib().cbf_hfwd(S=ptr(S), s_env=S.stride(1) // W, s_step=S.stride(0) // W, idx=ptr(idx), idx1=ptr(idx1),
-                        src=ptr(src), nev=ptr(nev), B=B, T=T, N=N, K=K, wpack=ptr(wpack), f_fwd=int(f_fwd), wrm=ptr(wrm),
-                        wvec=ptr(wvec), h_out=ptr(h_out), mask_out=ptr(mask_out), dim=D, num_blocks=nb, prec=f16,
-                        u_begin=int(u_begin), u_end=int(u_end or 0), dist_eps=float(C.CBF_DIST_EPS_COORD * D),
-                        stream=stream_handle(), **CBF_CONSTS)
-    _ok(rc, "cbf_hfwd")
+    kw = dict(S=ptr(S), s_env=S.stride(1) // W, s_step=S.stride(0) // W, idx=ptr(idx), idx1=ptr(idx1),
+              src=ptr(src), nev=ptr(nev), B=B, T=T, N=N, K=K, wpack=ptr(wpack), f_fwd=int(f_fwd), wrm=ptr(wrm),
+              wvec=ptr(wvec), h_out=ptr(h_out), mask_out=ptr(mask_out), dim=D, u_begin=int(u_begin),
+              u_end=int(u_end or 0), dist_eps=float(C.CBF_DIST_EPS_COORD * D), **CBF_CONSTS)
+    return kw, f16, 0 if u_end is not None and u_end == u_begin else nb
+
+
+def cbf_hfwd(S, idx, idx1, src, nev, wpack, f_fwd, wrm, wvec, h_out, mask_out, num_blocks=None,
+             u_begin=0, u_end=None, prec=None):
+    """h (masked) and the radius mask of every evaluation u_begin <= u < (u_end or nev) of the
+    deduplicated list: S (>= T+1, B, N, W); idx / idx1 (T, B, N, K) (idx1 = idx for
+    reuse_nbr_idx); src, h_out, mask_out (>= 2E,). Weights: w1f fragments at f_fwd of wpack + the
+    row-major W2|W3 image. A host range [u_begin, u_end) within the main slots (u_end <= E) needs
+    neither src nor nev contents: the rollout evaluates step t's main slots (idx[:t+1]) while
+    later steps are still being simulated."""
+    kw, f16, nb = _cbf_hfwd_kw(S, idx, idx1, src, nev, wpack, f_fwd, wrm, wvec, h_out, mask_out, num_blocks, u_begin,
+                               u_end, prec)
+    if nb:
+        _ok(lib().cbf_hfwd(num_blocks=nb, prec=f16, stream=stream_handle(), **kw), "cbf_hfwd")
     return nb
 
 
@@ -754,9 +786,8 @@ def cbf_bwd(S, idx, dh, wpack, f_bwd, wrm, wvec, *, passes=2, dE=None, partial=N
     return nb
 
 
-def rev_csr(idx, rptr, redges, n_nodes=None):
-    """idx (G, N, K) int32 contiguous -> rptr (G, Nn+1), redges (G, N*K); Nn = n_nodes (agents +
-    obstacle points, default N)."""
+def _rev_csr_kw(idx, rptr, redges, n_nodes=None):
+    """rev_csr's checks -> the CsrArgs fields (csrc/args.h) as a dict."""
     Gn, N, K = idx.shape
     Nn = N if n_nodes is None else int(n_nodes)
     check(idx, torch.int32, (Gn, N, K), "idx")
@@ -765,8 +796,13 @@ def rev_csr(idx, rptr, redges, n_nodes=None):
     ws = None
     if (2 * Nn + 1) * 4 > 150 * 1024:         # counters beyond LDS: csrc/graph.hip global path
         ws = _workspace("csr", Gn * Nn * 4, idx.device)
-    _ok(lib().rev_csr(idx=ptr(idx), G=Gn, N=N, K=K, ptr=ptr(rptr), edges=ptr(redges), Nn=Nn, ws=ptr(ws),
-                      stream=stream_handle()), "rev_csr")
+    return dict(idx=ptr(idx), G=Gn, N=N, K=K, ptr=ptr(rptr), edges=ptr(redges), Nn=Nn, ws=ptr(ws))
+
+
+def rev_csr(idx, rptr, redges, n_nodes=None):
+    """idx (G, N, K) int32 contiguous -> rptr (G, Nn+1), redges (G, N*K); Nn = n_nodes (agents +
+    obstacle points, default N)."""
+    _ok(lib().rev_csr(stream=stream_handle(), **_rev_csr_kw(idx, rptr, redges, n_nodes)), "rev_csr")
 
 
 def node_reduce(dE, rptr, redges, out, *, T, B, N, K, passes=2, accumulate=False, pass_mask=0, shift1=0,
@@ -1545,8 +1581,6 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     pc = _half(cw, "controller wpack", cmp_.prec)
     _ep(cw, cw.dtype, tuple(cw.shape), "controller wpack")
     _ep(cv, torch.float32, tuple(cv.shape) if isinstance(cv, torch.Tensor) else (), "controller wvec")
-    if cv.numel() < 352 or cw.numel() < (cmp_.off["nw1f"] + 54) * 512 * _planes(pc):
-        raise NativeError("packed controller weights too small")
     _ep(buf.get("pooled"), cw.dtype, (B, N, _prow(pc)), "pooled")
     _ep(buf.get("argmax"), torch.uint8, (B, N, 128), "argmax")
     filt = bool(refine) and loops > 0
@@ -1572,10 +1606,6 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     _ep_device(**{k: t for k, t in buf.items() if isinstance(t, torch.Tensor)}, ctrl_wpack=cw, ctrl_wvec=cv,
                cbf_wpack=bw, cbf_wvec=bv, cbf_wrm=brm)
     dev = S0.device
-    ws, ws_f4 = scan_ws(B, Nn, dev)
-    csr_ws = None
-    if filt and (2 * Nn + 1) * 4 > 150 * 1024:
-        csr_ws = _workspace("csr", B * Nn * 4, dev)
     E = B * N * K
     global _EPISODE_DRIVER
     if _EPISODE_DRIVER is None:
@@ -1588,15 +1618,20 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     flt = _refine_kw(B, N, Nn, K, D, None, g("idx"), g("A"), g("delta"), g("h"), bw, bmp.off["w1f"], brm, bv, g("rptr"),
                      g("redges"), lr, env_active=g("active"), dEv=ptr(g("dEv") if mode == 1 else None), ctl=ep["ctl"],
                      ew=ep["ew"], loops=loops, num_blocks=refine_grid(E, dev, qc), prec=qc) if filt else None
-    cfg = dict(episode=ep, refine=flt, Nn=Nn, K=K, num_cu=num_cu(dev), prec_ctrl=pc,
-               apw=ctrl_fwd_apw(B * N, dev, N), max_steps=max_steps, check_every=check_every,
-               mask_done=int(bool(mask_done)), cbf_blocks=cbf_fwd_grid(E, dev) if filt else 0,
-               f_edge=int(cmp_.off["ew1f"]), f_node=int(cmp_.off["nw1f"]),
-               L=float(max(1.0, N / C.AGENT_DENSITY) ** (1.0 / D)), **SCAN_CONSTS,
-               obs_r=float(C.OBS_RADIUS), sqrt3=float(C.SQRT3), loss_consts=LOSS_CONSTS,
-               S0=ptr(S0), S1=ptr(g("S1")), idx=ptr(g("idx")), pooled=ptr(g("pooled")), argmax=ptr(g("argmax")),
-               perm=ptr(g("perm")), ctrl_w=ptr(cw), ctrl_v=ptr(cv), csr_ws=ptr(csr_ws), scan_ws=ptr(ws),
-               scan_ws_env=int(ws_f4), stream=stream_handle())
+    # the step's launches on S0 (the driver swaps the record buffers): one scan with the kNN lists and the
+    # safety count, the safety-only scan of the final state, the controller, and the filter's h(s_t) and CSR
+    cs, sc = _scan_kw(S0, g("idx"), None, None, g("safe"), K=K, perm=g("perm"), n_agents=N)
+    _, fin = _scan_kw(S0, None, None, None, g("safe"), K=1, do_knn=False, perm=g("perm"), n_agents=N)
+    ck, pc, ncu = _ctrl_fwd_kw(S0, g("G"), g("idx"), cw, cmp_.off["ew1f"], cmp_.off["nw1f"], cv, g("A"), None, None, None,
+                               pooled=g("pooled"), argmax=g("argmax"), prec=cmp_.prec)
+    cbf_kw, nb = None, 0
+    if filt:
+        cbf_kw, _, nb = _cbf_fwd_kw(S0[None], g("idx")[None], bw, bmp.off["w1f"], bv, two=False, h_out=g("h")[None],
+                                    prec=bmp.prec)
+    cfg = dict(episode=ep, refine=flt, cell_sort=cs, scan=sc, scan_final=fin, ctrl=ck, cbf=cbf_kw,
+               csr=_rev_csr_kw(g("idx"), g("rptr"), g("redges"), Nn) if filt else None, S1=ptr(g("S1")), num_cu=ncu,
+               prec_ctrl=pc, cbf_blocks=nb, max_steps=max_steps, check_every=check_every,
+               mask_done=int(bool(mask_done)), stream=stream_handle())
     try:
         steps, cur = _EPISODE_DRIVER.run(cfg)
     except (RuntimeError, ValueError) as e:

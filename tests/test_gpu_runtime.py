@@ -29,26 +29,35 @@ def _trainer(acts=False, small=False, **kw):
     return tr
 
 
-def _rollout(tr, native_rollout, s0, g, early_stop):
+def _rollout(tr, native_rollout, s0, g, early_stop, obs=None):
     eng = tr.engine
     eng.native_rollout = native_rollout
-    T = eng.rollout(s0, g, early_stop=early_stop)
+    T = eng.rollout(s0, g, obs, early_stop=early_stop)
     torch.cuda.synchronize()
     BNK = eng.B * eng.N * eng.K
     return (T, eng.S[: T + 1].clone(), eng.idx[:T].clone(), eng.A[:T].clone(), eng.dist[:T].clone(),
             eng.safe[: T + 1].clone(), eng.hbuf[: T * BNK].clone(), eng.hmask[: T * BNK].clone())
 
 
-@pytest.mark.parametrize("early_stop", [True, False])
-def test_native_rollout_matches_python_loop(early_stop):
-    tr = _trainer()
+# 3d_obstacle: 8-float records and 12 obstacle nodes behind the agents (Nn > N); overlap: the CBF h
+# slices of the side stream, so hbuf / hmask are compared with what the slices wrote
+@pytest.mark.parametrize("early_stop,overlap,scene", [(True, False, {}), (False, False, {}),
+                                                      (False, False, dict(dim=3, num_obstacles=1)), (True, True, {})],
+                         ids=["True", "False", "3d_obstacle", "overlap"])
+def test_native_rollout_matches_python_loop(early_stop, overlap, scene):
+    tr = _trainer(**scene)
     tr.engine.check_every = 1
-    s0, g, _ = tr.sample()
-    a = _rollout(tr, False, s0, g, early_stop)
-    b = _rollout(tr, True, s0, g, early_stop)
+    tr.engine.overlap_hfwd = overlap            # before the driver is built (lazily, at the first native rollout)
+    s0, g, obs = tr.sample()
+    a = _rollout(tr, False, s0, g, early_stop, obs)
+    b = _rollout(tr, True, s0, g, early_stop, obs)
     assert a[0] == b[0]
     if early_stop:
         assert a[0] < tr.cfg.inner_loops          # the early stop triggered
+    if overlap:
+        assert a[6].abs().sum() > 0 and a[7].any()        # the slices ran
+    if scene:
+        assert tr.engine.Nn == tr.engine.N + 12 and tr.engine.W == 8
     for x, y in zip(a[1:], b[1:]):
         assert torch.equal(x, y)
 

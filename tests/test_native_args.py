@@ -115,6 +115,22 @@ def test_ext_extra_and_missing_keys(ext):
                                     max_scale=1.0, stats_row=0, oK=0))
 
 
+def _zeros(keys):
+    return dict.fromkeys(keys, 0)
+
+
+# the drivers' own keys (csrc/runtime.cpp) and the fields of the structs their sub-dicts fill (csrc/fill.h)
+ROLLOUT_OWN = ("Tmax resort_every check_every hfwd_blocks num_cu prec host_dist done_thr publish poll_query_ms small_ctl "
+               "small_apw knn_tail small_stamps node_acts node_act_bytes").split()
+BPTT_OWN = "Tmax prec nb_node nb_edge step_rows node_part edge_part fused_step node_acts node_act_bytes dS Gb rptr redges".split()
+SORT_KEYS = "S s_env B N rec L perm".split()
+SCAN_KEYS = ("S s_env perm B N K Nn dim idx i_env dang cnt c_env safe sf_env r2_train ttc_train r2_check ttc_check do_knn "
+             "do_safety prev_idx pi_env ws ws_env lanes stamps").split()
+CTRL_KEYS = ("S s_env dim G idx i_env B N K wpack f_edge f_node wvec A a_env Snext sn_env dist_sum d_env act_sum ac_env "
+             "noise n_env noise_key noise_prob noise_scale noise_t dt obs_r sqrt3 pooled p_env argmax am_env apw stamps").split()
+EDGE_KEYS = "S s_env dim idx i_env argmax am_env dP dp_env B N K wpack f_ew1f f_ew2tn dEc de_env partial init qsplit".split()
+
+
 def test_ext_drivers_and_commit_dict(ext):
     # an empty commit dict is a dict with every key missing, not None
     with pytest.raises(TypeError, match=r"pack_gather: missing argument 'ok'"):
@@ -129,10 +145,34 @@ def test_ext_drivers_and_commit_dict(ext):
     with pytest.raises(native.NativeError, match="no edge stamps"):
         native.ctrl_bwd_step({}, dict(stamps=torch.zeros(1)), 1)
     # the drivers read their config dicts the same way, before they touch the device
-    with pytest.raises(TypeError, match=r"RolloutDriver: missing argument 'B'"):
+    with pytest.raises(TypeError, match=r"RolloutDriver: missing argument 'Tmax'"):
         ext.RolloutDriver({})
-    with pytest.raises(TypeError, match=r"BpttDriver: argument 'B' must be int, got str"):
-        ext.BpttDriver({"B": "2"})
+    with pytest.raises(TypeError, match=r"BpttDriver: argument 'Tmax' must be int, got str"):
+        ext.BpttDriver({"Tmax": "2"})
+    # a key nothing reads is refused, by both training drivers (a complete config of zeros gets as far as
+    # the dimension check, still before any device call)
+    roll = dict(_zeros(ROLLOUT_OWN), hfwd=None, cell_sort=_zeros(SORT_KEYS), scan=_zeros(SCAN_KEYS), ctrl=_zeros(CTRL_KEYS))
+    bptt = dict(_zeros(BPTT_OWN), node=dict(_zeros(NODE_KEYS), act_coef=0.0, dt=0.0, sqrt3=0.0), edge=_zeros(EDGE_KEYS))
+    with pytest.raises(ValueError, match="RolloutDriver: bad dimensions"):
+        ext.RolloutDriver(roll)
+    with pytest.raises(ValueError, match="BpttDriver: bad dimensions"):
+        ext.BpttDriver(bptt)
+    with pytest.raises(TypeError, match=r"RolloutDriver: unexpected argument 'check_evry'"):
+        ext.RolloutDriver(dict(roll, check_evry=1))
+    with pytest.raises(TypeError, match=r"BpttDriver: unexpected argument 'gscale'"):
+        ext.BpttDriver(dict(bptt, gscale=0))
+    # a sub-dict is read by the launcher's own fill function, under the driver's and its own name
+    with pytest.raises(TypeError, match=r"RolloutDriver ctrl: missing argument 'apw'"):
+        ext.RolloutDriver(dict(roll, ctrl=_zeros(k for k in CTRL_KEYS if k != "apw")))
+    with pytest.raises(TypeError, match=r"RolloutDriver scan: unexpected argument 'num_cu'"):
+        ext.RolloutDriver(dict(roll, scan=dict(roll["scan"], num_cu=1)))
+    with pytest.raises(TypeError, match=r"BpttDriver edge: missing argument 'S'"):
+        ext.BpttDriver(dict(bptt, edge={}))
+    # hfwd=None (no overlapped CBF slices) is accepted: the next key is asked for
+    with pytest.raises(TypeError, match=r"RolloutDriver: missing argument 'cell_sort'"):
+        ext.RolloutDriver(dict(_zeros(ROLLOUT_OWN), hfwd=None))
+    with pytest.raises(TypeError, match=r"RolloutDriver: argument 'hfwd' must be a dict, got int"):
+        ext.RolloutDriver(dict(_zeros(ROLLOUT_OWN), hfwd=0))
 
 
 def test_ext_precision_code_outside_range(ext):
