@@ -222,6 +222,10 @@ struct RefineArgs {
   // here is left out: its edges are "not in the tile", its delta stays zero, and the control
   // words count the other envs alone.
   const uint8_t* env_active;
+  // per-axis actuator limit (0: off). `a` then holds the clamped actions and every update projects
+  // delta onto [-a_max - a, a_max - a], so a + delta stays in the box (up to the one rounding the
+  // caller's final clamp removes)
+  float a_max;
 };
 
 // Persistent safety filter for small envs (refine.hip refine_small_kernel): one workgroup per env
@@ -418,10 +422,13 @@ struct GradAssembleArgs {
 // (scan, controller, safety filter), all on one stream. Every count lives on the device.
 constexpr int EP_ALIVE = 0, EP_SAFE = 1, EP_ENV_STEPS = 2, EP_STEPS = 3, EP_ITERS = 4, EP_WORDS = 5;
 constexpr int EP_OUT = 8;                  // result words, the order of validate.COUNTS
+// action statistics (evaluate.ACTION_STATS), over the agents of the envs active at the step's start
+constexpr int EP_ACT_LIMITED = 0, EP_ACT_INTERVENED = 1, EP_ACT_DELTA = 2, EP_ACT_MAX = 3, EP_ACT_WORDS = 4;
+constexpr double FX_DELTA = 1048576.0;     // 2^20: fixed-point scale of the |delta| sum
 struct EpisodeArgs {
   const float4* S_cur; float4* S_next; long s_env;   // node records of s_t / s_{t+1} (strides in records)
   int dim, B, N;
-  const float* A;                          // (B,N,D) controller actions
+  float* A;                                // (B,N,D) controller actions (episode_limit clamps them in place)
   float* delta;                            // (B,N,D) filter correction or null; zeroed once it is read
   const float* G;                          // (B,N,D) goals
   float dt;
@@ -435,11 +442,18 @@ struct EpisodeArgs {
   unsigned long long thr_fx;               // DIST_MIN_CHECK * N * FX_DIST
   float thr;                               // DIST_MIN_CHECK
   long long* out;                          // EP_OUT result words (episode_final)
+  float a_max;                             // per-axis actuator limit on the applied action (0: off)
+  // EP_ACT_WORDS running action statistics, zero at the start (or null: not counted): agents with a
+  // component at the limit, agents with a non-zero correction, sum of |delta| * FX_DELTA, and the
+  // largest |u| as the bit pattern of the non-negative float
+  long long* act_st;
+  long long* act_out;                      // EP_ACT_WORDS result words (episode_final), with act_st
 };
 
 }  // namespace mb
 
 extern "C" {
+int mb_episode_limit(const mb::EpisodeArgs* a, hipStream_t st);
 int mb_episode_advance(const mb::EpisodeArgs* a, hipStream_t st);
 int mb_episode_tally(const mb::EpisodeArgs* a, hipStream_t st);
 int mb_episode_final(const mb::EpisodeArgs* a, hipStream_t st);

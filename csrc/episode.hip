@@ -1,8 +1,12 @@
 // Closed-loop episodes on the device, gfx950: the per-step glue of a batch of episodes (validation
 // during training, evaluation) between the scan, the controller and the safety filter.
 //
-//   episode_advance_kernel  one thread per agent: u = a + delta, s' = s + [v, u] * dt (or s, once every
-//     env is done), the record of S_next, and the env's goal-distance sum in fixed point.
+//   episode_limit_kernel    (with an actuator limit only) one thread per action component: the
+//     controller's action clamped to [-a_max, a_max] in place, before the filter reads it.
+//   episode_advance_kernel  one thread per agent: u = a + delta (clamped to the box under a limit),
+//     s' = s + [v, u] * dt (or s, once every env is done), the record of S_next, the env's
+//     goal-distance sum in fixed point and, when asked for, the action statistics of the agents whose
+//     env is active at the start of the step.
 //   episode_tally_kernel    one workgroup per step: the integer totals, the per-env done mask, the
 //     "some env still runs" word, the filter's iteration count; clears the per-step accumulators.
 //   episode_final_kernel    one workgroup, after the safety-only scan of the final state: the result
@@ -34,6 +38,31 @@ DEV float episode_goal_dist(const float (&p)[D], const float* g) {
   return sqrtf(sqsum<D>(e));
 }
 
+// |delta| in 2^-20 fixed point, rounded half-even per component; NaN / Inf / out of range -> FX_SAT
+DEV unsigned long long episode_delta_fx(float d) {
+  const double x = (double)fabsf(d) * FX_DELTA;
+  return (x >= 0.0 && x < FX_SAT) ? (unsigned long long)__double2ll_rn(x) : (unsigned long long)FX_SAT;
+}
+
+// torch.clamp(v, -m, m): comparisons, so a NaN stays a NaN
+DEV float episode_clamp(float v, float m) { return v < -m ? -m : (v > m ? m : v); }
+
+DEV unsigned wave_max_u32(unsigned v) {
+  static_for<6>([&](auto o_) {
+    constexpr int O = 32 >> decltype(o_)::value;
+    const unsigned w = lane_xor<O>(v);
+    v = w > v ? w : v;
+  });
+  return v;
+}
+
+template <int D>
+__global__ __launch_bounds__(EP_BLOCK) void episode_limit_kernel(EpisodeArgs a) {
+  const long total = (long)a.B * a.N * D;
+  const long x = (long)blockIdx.x * EP_BLOCK + threadIdx.x;
+  if (x < total) a.A[x] = episode_clamp(a.A[x], a.a_max);
+}
+
 template <int D>
 __global__ __launch_bounds__(EP_BLOCK) void episode_advance_kernel(EpisodeArgs a) {
   const long total = (long)a.B * a.N;
@@ -42,15 +71,48 @@ __global__ __launch_bounds__(EP_BLOCK) void episode_advance_kernel(EpisodeArgs a
   const long gc = ok ? gid : total - 1;                 // clamped: every lane stays for the wave sum
   const int b = (int)(gc / a.N), i = (int)(gc % a.N);   // per lane: a wave can straddle two envs
   const bool alive = a.st[EP_ALIVE] != 0;
-  float p[D], v[D], u[D];
+  const bool limit = a.a_max > 0.f;                     // scalar: a kernel argument
+  float p[D], v[D], u[D], dl[D];
   load_rec<D>(a.S_cur + (size_t)b * a.s_env * REC<D>, (unsigned)i, p, v);
 #pragma unroll
-  for (int q = 0; q < D; ++q) u[q] = a.A[gc * D + q];
+  for (int q = 0; q < D; ++q) { u[q] = a.A[gc * D + q]; dl[q] = 0.f; }
   if (a.delta) {
 #pragma unroll
     for (int q = 0; q < D; ++q) {
-      u[q] = u[q] + a.delta[gc * D + q];
+      dl[q] = a.delta[gc * D + q];
+      u[q] = u[q] + dl[q];
       if (ok) a.delta[gc * D + q] = 0.f;                // the next step's filter starts from zero
+    }
+  }
+  if (limit) {                                          // removes the one rounding by which a + hi can pass a_max
+#pragma unroll
+    for (int q = 0; q < D; ++q) u[q] = episode_clamp(u[q], a.a_max);
+  }
+  if (a.act_st) {
+    // the agents of the envs that are active at the start of the step (the tally has not run yet);
+    // per-wave integer sums / max, then one integer atomic each: order independent
+    const bool on = ok && a.active[b] != 0;
+    bool at = false, iv = false;
+    unsigned long long dsum = 0ull;
+    unsigned mx = 0u;
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+      const float au = fabsf(u[q]);
+      at |= limit && au == a.a_max;
+      iv |= dl[q] != 0.f;
+      dsum += episode_delta_fx(dl[q]);
+      const unsigned bits = __float_as_uint(au);
+      mx = bits > mx ? bits : mx;
+    }
+    const unsigned long long n_at = wave_sum_u64(on && at ? 1ull : 0ull), n_iv = wave_sum_u64(on && iv ? 1ull : 0ull);
+    const unsigned long long d_all = wave_sum_u64(on ? dsum : 0ull);
+    const unsigned m_all = wave_max_u32(on ? mx : 0u);
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+      unsigned long long* w = reinterpret_cast<unsigned long long*>(a.act_st);
+      if (n_at) atomicAdd(w + EP_ACT_LIMITED, n_at);
+      if (n_iv) atomicAdd(w + EP_ACT_INTERVENED, n_iv);
+      if (d_all) atomicAdd(w + EP_ACT_DELTA, d_all);
+      if (m_all) atomicMax(w + EP_ACT_MAX, (unsigned long long)m_all);
     }
   }
   if (alive) {
@@ -152,6 +214,8 @@ __global__ __launch_bounds__(EP_BLOCK) void episode_final_kernel(EpisodeArgs a) 
     a.out[5] = a.st[EP_ITERS];
     a.out[6] = a.st[EP_STEPS];
     a.out[7] = (long long)((s_dist + (1ull << 11)) >> 12);   // 2^-32 -> the 2^-20 of validate.DIST_FX
+    if (a.act_st && a.act_out)
+      for (int w = 0; w < EP_ACT_WORDS; ++w) a.act_out[w] = a.act_st[w];
   }
 }
 
@@ -164,10 +228,23 @@ static int episode_check(const EpisodeArgs* a) {
 
 }  // namespace mb
 
+// the controller's actions clamped to the actuator box, in place (a_max > 0)
+extern "C" int mb_episode_limit(const mb::EpisodeArgs* a, hipStream_t st) {
+  using namespace mb;
+  if (a->B < 1 || a->N < 1 || (a->dim != 2 && a->dim != 3) || !(a->a_max > 0.f)) return -1;
+  if ((long)a->B * a->N >= (1l << 31) - 65536) return -3;
+  if (!a->A) return -2;
+  const dim3 grid((unsigned)(((long)a->B * a->N * a->dim + EP_BLOCK - 1) / EP_BLOCK));
+  if (a->dim == 3) hipLaunchKernelGGL(episode_limit_kernel<3>, grid, dim3(EP_BLOCK), 0, st, *a);
+  else hipLaunchKernelGGL(episode_limit_kernel<2>, grid, dim3(EP_BLOCK), 0, st, *a);
+  return (int)hipGetLastError();
+}
+
 extern "C" int mb_episode_advance(const mb::EpisodeArgs* a, hipStream_t st) {
   using namespace mb;
   if (const int rc = episode_check(a)) return rc;
-  if (!a->S_next || !a->A || !a->dist_fx || a->S_next == a->S_cur) return -2;
+  if (!a->S_next || !a->A || !a->dist_fx || a->S_next == a->S_cur || (a->act_st && !a->active)) return -2;
+  if (a->a_max < 0.f || a->a_max != a->a_max) return -1;
   const dim3 grid((unsigned)(((long)a->B * a->N + EP_BLOCK - 1) / EP_BLOCK));
   if (a->dim == 3) hipLaunchKernelGGL(episode_advance_kernel<3>, grid, dim3(EP_BLOCK), 0, st, *a);
   else hipLaunchKernelGGL(episode_advance_kernel<2>, grid, dim3(EP_BLOCK), 0, st, *a);

@@ -22,6 +22,10 @@
 // (wave-uniform: tiles straddle envs whenever N*K is no multiple of 32), and the update leaves the
 // env's delta at zero. The control words then count the other envs alone, so a batch stops when
 // its live envs are clean, exactly as the filter run on those envs alone would.
+// Actuator limit (a_max > 0, optional): `a` arrives clamped to the box [-a_max, a_max]^D and every
+// update projects delta onto [-a_max - a, a_max - a] after the gradient step, behind one scalar test
+// of the kernel argument (off: the instructions of the unlimited filter). The early-out rule is
+// unchanged: a saturated agent can keep an edge active for all the iterations.
 // Small envs (at most 64 graph nodes): refine_small_kernel runs the whole loop of an env in one
 // workgroup and one launch, with the same per-tile body (refine_tile) and the same update
 // (refine_node_grad, refine_step) on LDS copies, and per-env result words instead of atomics.
@@ -358,6 +362,12 @@ DEV void refine_node_grad(const float* dE, const int* ptr, const int* edges, int
 }
 // the gradient step of one delta component: d s'_v / d delta = dt
 DEV float refine_step(float d, float lr, float dt, float g) { return d - lr * (dt * g); }
+// the projection of one delta component onto the actuator box: ac + delta in [-a_max, a_max] for the
+// clamped action ac. Comparisons, not fminf / fmaxf: a NaN stays a NaN, as in torch.clamp.
+DEV float refine_project(float d, float ac, float a_max) {
+  const float lo = -a_max - ac, hi = a_max - ac;
+  return d < lo ? lo : (d > hi ? hi : d);
+}
 
 template <int NW, int D>
 __global__ __launch_bounds__(NW * 64, 1) void refine_small_kernel(RefineSmallArgs sa) {
@@ -435,6 +445,11 @@ __global__ __launch_bounds__(NW * 64, 1) void refine_small_kernel(RefineSmallArg
         float* d = dl + (size_t)i * D;
 #pragma unroll
         for (int q = 0; q < D; ++q) d[q] = refine_step(d[q], a.lr, a.dt, g[q]);
+        if (a.a_max > 0.f) {                              // scalar: a kernel argument
+          const float* ac = al + (size_t)i * D;
+#pragma unroll
+          for (int q = 0; q < D; ++q) d[q] = refine_project(d[q], ac[q], a.a_max);
+        }
       }
     }
     __syncthreads();
@@ -513,6 +528,11 @@ __global__ __launch_bounds__(256) void refine_update_kernel(RefineArgs a) {
   float* d = a.delta + ((size_t)b * N + i) * D;
 #pragma unroll
   for (int q = 0; q < D; ++q) d[q] = MB_PREC::refine_step(d[q], a.lr, a.dt, g[q]);
+  if (a.a_max > 0.f) {                                     // scalar: a kernel argument
+    const float* ac = a.a + ((size_t)b * N + i) * D;
+#pragma unroll
+    for (int q = 0; q < D; ++q) d[q] = MB_PREC::refine_project(d[q], ac[q], a.a_max);
+  }
 }
 
 }  // namespace mb
@@ -520,7 +540,7 @@ __global__ __launch_bounds__(256) void refine_update_kernel(RefineArgs a) {
 extern "C" int mb_refine_update(const mb::RefineArgs* a, hipStream_t st) {
   using namespace mb;
   if (a->K > 16 || a->K < 1 || a->B < 1 || a->N < 1 || a->Nn < a->N || a->it < 0) return -1;
-  if (!a->delta || !a->dEv || !a->ptr || !a->edges || !a->ctl) return -2;
+  if (!a->delta || !a->dEv || !a->ptr || !a->edges || !a->ctl || (a->a_max > 0.f && !a->a)) return -2;
   const long total = (long)a->B * a->N * RG;
   const dim3 grid((unsigned)((total + 255) / 256));
   if (a->dim == 3) hipLaunchKernelGGL(refine_update_kernel<3>, grid, dim3(256), 0, st, *a);

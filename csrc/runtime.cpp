@@ -471,6 +471,7 @@ RefineCall refine_call(Args& x) {
   x("obs_r", r.obs_r); x("dist_thr", r.dist_thr); x("dist_eps", r.dist_eps); x("hn_out", r.hn_out);
   x("flag_out", r.flag_out); x("env_active", r.env_active); x("loops", c.sa.loops); x.opt("ew", c.sa.ew);
   x.opt("num_blocks", c.num_blocks); x("prec", c.prec);
+  x.opt("a_max", r.a_max);                // the actuator limit: off (0) without the key
   return c;
 }
 
@@ -483,7 +484,7 @@ int refine_loop(const RefineCall* c, hipStream_t st) {
   mb::RefineArgs r = c->sa.r;
   const int loops = c->sa.loops;
   if ((r.dim != 2 && r.dim != 3) || r.B < 1 || r.N < 1 || r.Nn < r.N || r.K < 1 || r.K > 16 || loops < 0 ||
-      c->num_blocks < 1 || r.f_bwd < 0 || r.s_env < r.Nn || c->prec < 0 || c->prec > 2)
+      c->num_blocks < 1 || r.f_bwd < 0 || r.s_env < r.Nn || c->prec < 0 || c->prec > 2 || !(r.a_max >= 0.f))
     return -1;
   if (!r.S || !r.idx || !r.a || !r.delta || !r.h || !r.wpack || !r.wrm || !r.wvec || !r.dEv || !r.ptr || !r.edges || !r.ctl)
     return -2;
@@ -514,7 +515,7 @@ int refine_small(const RefineCall* c, hipStream_t st) {
   if (r.dim != 2 && r.dim != 3) return -1;
   if (r.B < 1 || r.N < 1 || r.Nn < r.N || r.K < 1 || r.K > 16 || c->sa.loops < 0 || r.f_bwd < 0 || r.s_env < r.Nn) return -1;
   if (r.Nn > 64) return -4;                                    // SMALL_MAXN: the env must fit one workgroup's LDS
-  if (c->prec < 0 || c->prec > 2) return -1;
+  if (c->prec < 0 || c->prec > 2 || !(r.a_max >= 0.f)) return -1;
   if (!r.S || !r.idx || !r.a || !r.delta || !r.h || !r.wpack || !r.wrm || !r.wvec || !r.ptr || !r.edges || !c->sa.ew) return -2;
   if (c->sa.loops == 0) return 0;
   return by_prec(c->prec, mb_refine_small, mb_refine_small_f16, mb_refine_small_x3)(&c->sa, st);
@@ -527,6 +528,8 @@ mb::EpisodeArgs episode_args(Args& x) {
   x("N", e.N); x("A", e.A); x("delta", e.delta); x("G", e.G); x("dt", e.dt); x("st", e.st);
   x("dist_fx", e.dist_fx); x("safe", e.safe); x("active", e.active); x("prev_active", e.prev_active);
   x("ctl", e.ctl); x("ew", e.ew); x("loops", e.loops); x("mode", e.mode); x("thr", e.thr); x("out", e.out);
+  // the actuator limit and the action statistics: off without the keys
+  x.opt("a_max", e.a_max); x.opt("act_st", e.act_st); x.opt("act_out", e.act_out);
   e.thr_fx = (unsigned long long)std::llrint((double)e.thr * (double)e.N * mb::FX_DIST);
   return e;
 }
@@ -534,7 +537,8 @@ mb::EpisodeArgs episode_args(Args& x) {
 // Closed-loop episode driver (csrc/episode.hip): a whole batch of episodes -- validation during
 // training, evaluation -- with or without the safety filter, as one call. Per step, on the caller's
 // stream: cell_sort + ONE scan of s_t (kNN and the safety count of the step before), the controller
-// forward, the filter (cbf_fwd for h(s_t), rev_csr, refine_loop or refine_small), episode_advance,
+// forward, with an actuator limit episode_limit, the filter (cbf_fwd for h(s_t), rev_csr, refine_loop
+// or refine_small), episode_advance,
 // episode_tally, and a swap of the two record buffers. The buffers come from Python
 // (ops/episode.py), validated there once per call; nothing is allocated and the host does not wait
 // inside a step. Every check_every steps the "some env still runs" word is copied to pinned memory
@@ -607,6 +611,8 @@ class EpisodeDriver {
         f.perm != s.perm || g.sort.perm != s.perm || !e.safe || s.safe != e.safe || f.safe != e.safe || !e.st || !e.dist_fx ||
         !e.active || !e.prev_active || !e.out || !a.wpack || !a.wvec || (g.prec_ctrl == 2 && !a.pooled))
       throw std::invalid_argument("EpisodeDriver: a required buffer is missing");
+    if (!(e.a_max >= 0.f) || (e.act_st != nullptr) != (e.act_out != nullptr) || (filter && g.r.sa.r.a_max != e.a_max))
+      throw std::invalid_argument("EpisodeDriver: bad actuator limit or action-statistics words");
     if (filter) {
       const mb::RefineArgs& r = g.r.sa.r;
       if (g.r.prec == 1) throw std::invalid_argument("EpisodeDriver: the safety filter has no fp16 build");
@@ -634,6 +640,7 @@ class EpisodeDriver {
       mb::CtrlArgs a = g.ctrl;
       a.S = S[cur];
       chk(by_prec(g.prec_ctrl, mb_ctrl_fwd, mb_ctrl_fwd_f16, mb_ctrl_fwd_x3)(&a, g.num_cu, st), "ctrl_fwd");
+      if (e.a_max > 0.f) chk(mb_episode_limit(&e, st), "episode_limit");     // before the filter reads A
       if (e.mode) refine(g, S[cur], st);
       e.S_cur = S[cur]; e.S_next = S[cur ^ 1];
       chk(mb_episode_advance(&e, st), "episode_advance");
@@ -681,6 +688,7 @@ void register_runtime(py::module& m) {
   def_launch(m, "refine_loop", refine_call, refine_loop);
   def_launch(m, "refine_small", refine_call, refine_small);
   // the three launches of csrc/episode.hip on their own, as EpisodeDriver issues them per step
+  def_launch(m, "episode_limit", episode_args, mb_episode_limit);
   def_launch(m, "episode_advance", episode_args, mb_episode_advance);
   def_launch(m, "episode_tally", episode_args, mb_episode_tally);
   def_launch(m, "episode_final", episode_args, mb_episode_final);

@@ -4,7 +4,7 @@
                        [--max_steps 50] [--no_refine] [--refine_space actions|gains] [--diagnose]
                        [--dim 2|3] [--num_obstacles M] [--dtype fp32|bf16|fp16]
                        [--refine_impl autograd|native] [--rollout_impl python|native]
-                       [--device auto|cpu|hip] [--gpu 0]
+                       [--a_max A] [--action_stats] [--device auto|cpu|hip] [--gpu 0]
 
 Prints one JSON line: safety rate, reaching rate, mean final goal distance, refinement
 iterations. Without --model_path the networks are random-initialised (plumbing check).
@@ -15,6 +15,9 @@ input layer and must agree with --dim); --dtype is the MFMA operand precision on
 --refine_impl native runs the refinement as the device-resident safety filter (HIP only);
 --rollout_impl native runs each batch of episodes as one native call (HIP only; with --no_refine
 or --refine_impl native, not with --diagnose or --refine_space gains).
+--a_max A limits every component of the applied action to [-A, A] (the nominal action is clamped,
+the filter projects onto the box; not with --diagnose or --refine_space gains) and, like
+--action_stats alone, adds limited_rate, intervention_rate, mean_abs_delta and max_abs_action.
 """
 from __future__ import annotations
 
@@ -43,6 +46,10 @@ def main(argv=None):
     ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32")
     ap.add_argument("--refine_impl", choices=["autograd", "native"], default="autograd")
     ap.add_argument("--rollout_impl", choices=["python", "native"], default="python")
+    ap.add_argument("--a_max", type=float, default=None,
+                    help="per-axis actuator limit |u| <= A on the applied action (default: none)")
+    ap.add_argument("--action_stats", action="store_true",
+                    help="report limited_rate, intervention_rate, mean_abs_delta and max_abs_action")
     args = ap.parse_args(argv)
     if args.gpu is not None:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)
@@ -69,7 +76,7 @@ def main(argv=None):
     cfg = EvalConfig(num_agents=args.num_agents, num_envs=args.num_envs, seed=args.seed, refine=not args.no_refine,
                      refine_space=args.refine_space, diagnose=args.diagnose, dim=args.dim,
                      num_obstacles=args.num_obstacles, dtype=args.dtype, refine_impl=args.refine_impl,
-                     rollout_impl=args.rollout_impl)
+                     rollout_impl=args.rollout_impl, a_max=args.a_max, action_stats=args.action_stats)
     if args.episodes is not None:
         cfg.episodes = args.episodes
     if args.max_steps is not None:
@@ -81,7 +88,7 @@ def main(argv=None):
     try:
         out = evaluate(ctrl, cbf, cfg, device=dev)
     except ValueError as e:
-        if cfg.rollout_impl != "native" or "rollout_impl" not in str(e):
+        if not ((cfg.rollout_impl == "native" and "rollout_impl" in str(e)) or (cfg.a_max is not None and "a_max" in str(e))):
             raise
         ap.error(str(e))
     out.update({"num_agents": args.num_agents, "num_envs": args.num_envs, "episodes": cfg.episodes,
@@ -89,6 +96,8 @@ def main(argv=None):
                 "refine_impl": cfg.refine_impl, "dtype": cfg.dtype})
     if cfg.rollout_impl != "python":
         out["rollout_impl"] = cfg.rollout_impl
+    if cfg.a_max is not None:
+        out["a_max"] = cfg.a_max
     print(json.dumps(out), flush=True)
     return out
 

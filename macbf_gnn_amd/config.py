@@ -105,6 +105,8 @@ class TrainConfig:
     val_refine_loops: int = REFINE_LOOPS
     val_impl: str = "python"          # "python": the rollout as torch ops | "native" (HIP only, opt-in): one
                                       # native call per rollout (ops/episode.py), the same integer totals
+    val_a_max: float = 0.0            # per-axis actuator limit |u| <= val_a_max on both validation rollouts
+                                      # (evaluate.py, "Actuator limit"); 0: off. Training rollouts are not touched
     save_best: bool = False           # keep <model_path>.best (+ .best.json) at the best validation so far
     best_metric: str = ""             # a val_*_rate key, higher is better; "": val_refined_safety_rate
                                       # (val_safety_rate with val_refine off)

@@ -21,9 +21,29 @@ On a HIP device the CBF and controller run through the native autograd Functions
 (``ops/cbf.py``, ``ops/ctrl.py``); on CPU through the fp32 oracle. ``refine_impl="native"`` (HIP
 only, opt-in) runs the action refinement as the device-resident safety filter of
 ``ops/refine.py`` (``csrc/refine.hip``) instead of the autograd loop.
+
+Actuator limit (``a_max``, opt-in; all of it in fp32). A per-axis box: every component of the applied
+action lies in [-a_max, a_max]. A box and not a norm ball because ``clamp`` is exact, so the Python
+and native paths agree bit for bit.
+    a_c   = clamp(a, -a_max, a_max)                      (nominal action)
+    lo    = -a_max - a_c,  hi = a_max - a_c              (one subtraction each)
+    delta <- min(max(delta - lr * (dt * g), lo), hi)     (the refinement step, then the projection;
+                                                          s' is formed from a_c + delta)
+    u     = clamp(a_c + delta, -a_max, a_max)            (applied action: the final clamp removes the
+                                                          one rounding by which a_c + hi can pass a_max)
+The early-out rule does not change: an iteration without an active edge ends the work, and a
+saturated agent can keep an edge active for all ``loops`` iterations.
+
+Action statistics (``ACTION_STATS``, with ``action_stats`` or a limit), over the agents of the envs
+that are active at the start of a step (the mask that weights ``agent_steps``): agents with some
+|u_q| == a_max, agents with some delta_q != 0, the sum over agents and components of
+round(|delta_q| * 2^20) (float64, half-even, per component: an integer sum, so it does not depend on
+the order) and the largest |u_q| (carried as the int bit pattern of the non-negative float and
+reduced by an integer max).
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -58,9 +78,71 @@ class EvalConfig:
     rollout_impl: str = "python"    # "python" or "native" (HIP only, opt-in): the whole batch of episodes as one
                                     # native call (ops/episode.py); needs refine off or refine_impl="native",
                                     # refine_space="actions", diagnose off and early_stop on
+    a_max: Optional[float] = None   # per-axis actuator limit on the applied action (module docstring); None: off.
+                                    # Not with refine_space="gains" or diagnose. Implies action_stats
+    action_stats: bool = False      # add limited_rate, intervention_rate, mean_abs_delta, max_abs_action
 
 
 MFMA_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+# the action statistics of a batch of episodes, an int64 vector: three sums, then a maximum
+ACTION_STATS = ("limited_agent_steps", "intervened_agent_steps", "delta_abs_fx", "action_abs_max")
+DELTA_FX = float(1 << 20)           # fixed-point scale of delta_abs_fx
+_FX_SAT = float(1 << 46)            # a non-finite or absurd |delta| term (csrc/args.h FX_SAT)
+
+
+def check_a_max(a_max) -> Optional[float]:
+    """None (off), or the limit as the fp32 value every path compares with."""
+    if a_max is None:
+        return None
+    a_max = float(a_max)
+    if not math.isfinite(a_max) or a_max <= 0.0:
+        raise ValueError(f"a_max must be a positive finite number (or None for no limit), got {a_max!r}")
+    m = float(torch.tensor(a_max, dtype=torch.float32))
+    if not math.isfinite(m) or m <= 0.0:
+        raise ValueError(f"a_max = {a_max!r} is not a positive finite fp32 number")
+    return m
+
+
+def check_action_limit(cfg: "EvalConfig") -> Optional[float]:
+    """``cfg.a_max`` checked (``check_a_max``); the options a limit cannot be combined with are errors
+    that name them."""
+    m = check_a_max(cfg.a_max)
+    if m is not None and cfg.refine and cfg.refine_space == "gains":
+        raise ValueError("a_max limits free actions: refine_space='gains' has the gain law's own bounds; use "
+                         "refine_space='actions' or a_max=None")
+    if m is not None and cfg.diagnose:
+        raise ValueError("a_max has no diagnose mode: use diagnose=False or a_max=None")
+    return m
+
+
+def action_stats(u, delta, active, a_max) -> torch.Tensor:
+    """``ACTION_STATS`` of one step: u (B, N, D) applied actions, delta (B, N, D) the filter's correction
+    or None (no filter), active (B,) bool the envs counted, a_max the fp32 limit or None -> int64 (4,)
+    on u's device. Nothing is read on the host."""
+    act = active.view(-1, 1)
+    au = u.detach().float().abs()
+    zero = torch.zeros((), dtype=torch.int64, device=u.device)
+    limited = ((au == a_max).any(-1) & act).sum() if a_max is not None else zero
+    amax = (au.contiguous().view(torch.int32).amax(-1).long() * act).max()
+    if delta is None:
+        return torch.stack([limited, zero, zero, amax])
+    d = delta.detach().float()
+    x = d.abs().double() * DELTA_FX
+    fx = torch.where((x >= 0) & (x < _FX_SAT), x.round(), torch.full_like(x, _FX_SAT)).long()
+    return torch.stack([limited, ((d != 0).any(-1) & act).sum(), (fx.sum(-1) * act).sum(), amax])
+
+
+def merge_action_stats(total, step):
+    """Running ``ACTION_STATS``: the sums add, the bit pattern of the largest |u| is an integer max."""
+    return torch.cat([total[:3] + step[:3], torch.maximum(total[3:], step[3:])])
+
+
+def action_metrics(c: Dict[str, int], agent_steps: int, D: int) -> Dict[str, float]:
+    """The four result keys from the integer statistics (a dict over ``ACTION_STATS``)."""
+    n = max(agent_steps, 1)
+    bits = torch.tensor(c["action_abs_max"], dtype=torch.int64).to(torch.int32)
+    return {"limited_rate": c["limited_agent_steps"] / n, "intervention_rate": c["intervened_agent_steps"] / n,
+            "mean_abs_delta": c["delta_abs_fx"] / DELTA_FX / (n * D), "max_abs_action": float(bits.view(torch.float32))}
 
 
 def _knn(s, k, obstacles=None):
@@ -88,9 +170,12 @@ def _euler(s, a):
 
 
 def refine_actions(cbf, s, a, idx, loops: int = C.REFINE_LOOPS, lr: float = C.REFINE_LEARNING_RATE,
-                   check_every: int = 10, obstacles=None):
+                   check_every: int = 10, obstacles=None, a_max=None, return_delta: bool = False):
     """Gradient refinement of the actions on the discrete CBF condition. Returns
     (refined actions, iterations used, remaining violation sum).
+
+    ``a_max``: the actuator limit of the module docstring -- the action is clamped first, every step is
+    projected onto [lo, hi] and the result is clamp(a_c + delta). ``return_delta`` appends ``delta``.
 
     The violation is a hinge: once it is exactly zero its gradient is exactly zero, so further
     iterations leave the actions unchanged. The loop therefore only looks at the violation on
@@ -99,8 +184,12 @@ def refine_actions(cbf, s, a, idx, loops: int = C.REFINE_LOOPS, lr: float = C.RE
 
     ``obstacles`` (B, M, D): static points among the neighbour slots of ``idx``; they have no action
     and do not move, so ``delta`` stays (B, N, D)."""
+    a_max = check_a_max(a_max)
     with torch.no_grad():
         h = cbf(s, idx=idx, obstacles=obstacles)
+        if a_max is not None:
+            a = a.clamp(-a_max, a_max)
+            lo, hi = -a_max - a, a_max - a
     delta = torch.zeros_like(a, requires_grad=True)
     viol = torch.zeros((), device=s.device)
     used = torch.zeros((), dtype=torch.int64, device=s.device)
@@ -117,7 +206,14 @@ def refine_actions(cbf, s, a, idx, loops: int = C.REFINE_LOOPS, lr: float = C.RE
         g, = torch.autograd.grad(viol, delta)
         with torch.no_grad():
             delta -= lr * g
-    return (a + delta).detach(), int(used), float(viol.detach())
+            if a_max is not None:
+                delta.copy_(torch.min(torch.max(delta, lo), hi))
+    out = (a + delta).detach()
+    if a_max is not None:
+        out = out.clamp(-a_max, a_max)
+    if return_delta:
+        return out, int(used), float(viol.detach()), delta.detach()
+    return out, int(used), float(viol.detach())
 
 
 def _pd_action(s, g, y):
@@ -197,17 +293,25 @@ def _rollout_native(controller, cbf, s0, g, cfg: EvalConfig, obstacles) -> Dict[
     from . import validate as V
     from .ops import episode
     B, N, _ = s0.shape
+    a_max = check_action_limit(cfg)
+    stats = cfg.action_stats or a_max is not None
     vec = episode.run_episodes(controller, cbf, s0, g, obstacles, refine=cfg.refine, loops=cfg.refine_loops,
                                lr=cfg.refine_lr, max_steps=cfg.max_steps, top_k=cfg.top_k, mask_done=False,
-                               check_every=V.CHECK_EVERY)
-    c = dict(zip(V.COUNTS, (int(x) for x in vec.tolist())))          # the one host read
+                               check_every=V.CHECK_EVERY, a_max=a_max, action_stats=stats)
+    if stats:
+        vec = torch.cat(vec)
+    tot = [int(x) for x in vec.tolist()]                             # the one host read
+    c = dict(zip(V.COUNTS, tot))
     # the Python loop's fp32 mean over a (B, N) 0 / 1 tensor, formed the same way from the count
     hit = torch.arange(B * N, device=s0.device).view(B, N) < c["reached_agents"]
-    return {"safety_rate": float(c["safe_agent_steps"]) / max(c["agent_steps"], 1),
-            "reaching_rate": float(hit.float().mean()),
-            "mean_goal_dist": c["goal_dist_fx"] / V.DIST_FX / max(c["agents"], 1),
-            "steps": c["steps"], "agent_steps": c["agent_steps"],
-            "refine_iters": c["refine_iters"]}
+    out = {"safety_rate": float(c["safe_agent_steps"]) / max(c["agent_steps"], 1),
+           "reaching_rate": float(hit.float().mean()),
+           "mean_goal_dist": c["goal_dist_fx"] / V.DIST_FX / max(c["agents"], 1),
+           "steps": c["steps"], "agent_steps": c["agent_steps"],
+           "refine_iters": c["refine_iters"]}
+    if stats:
+        out.update(action_metrics(dict(zip(ACTION_STATS, tot[len(V.COUNTS):])), c["agent_steps"], s0.shape[-1] // 2))
+    return out
 
 
 def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dict[str, float]:
@@ -216,6 +320,8 @@ def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dic
     if cfg.refine_impl not in ("autograd", "native"):
         raise ValueError(f"unknown refine_impl {cfg.refine_impl!r} (autograd or native)")
     check_rollout_impl(cfg, s0.device)
+    a_max = check_action_limit(cfg)
+    stats = cfg.action_stats or a_max is not None
     if cfg.rollout_impl == "native":
         return _rollout_native(controller, cbf, s0, g, cfg, obstacles)
     native_filter = cfg.refine and cfg.refine_impl == "native" and cfg.refine_space != "gains"
@@ -234,25 +340,33 @@ def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dic
     unsafe_n = torch.zeros((), device=s.device)
     seen_n = torch.zeros((), device=s.device)
     active = torch.ones(B, dtype=torch.bool, device=s.device)
+    acts = torch.zeros(len(ACTION_STATS), dtype=torch.int64, device=s.device)     # read once per episode
     for t in range(cfg.max_steps):
         idx = _knn(s, k, obs)
         with torch.no_grad():
             a = controller(s, g, idx=idx, obstacles=obs)
+            if a_max is not None:
+                a = a.clamp(-a_max, a_max)
+        a_nom, delta = a, None
         if cfg.refine and cfg.refine_space == "gains":
             with torch.no_grad():
                 nodes = None if obs is None else oracle.with_obstacles(s, obs)
                 _, aux = oracle.controller_forward(controller.params_dict(), s, g, idx, return_aux=True, nodes=nodes)
             a, it, _ = refine_gains(cbf, s, g, aux["gains"], idx, cfg.refine_loops, cfg.refine_lr, obstacles=obs)
             refine_iters += it
+            delta = a - a_nom                       # the gain law has no delta of its own: what it changed
         elif native_filter:
             from .ops import refine as refine_ops
-            a, used, _ = refine_ops.safety_filter(cbf, s, a, idx, obstacles=obs, loops=cfg.refine_loops,
-                                                  lr=cfg.refine_lr)
+            a, used, _, delta = refine_ops.safety_filter(cbf, s, a, idx, obstacles=obs, loops=cfg.refine_loops,
+                                                         lr=cfg.refine_lr, a_max=a_max, return_delta=True)
             iters_dev += used
         elif cfg.refine:
-            a, it, _ = refine_actions(cbf, s, a, idx, cfg.refine_loops, cfg.refine_lr, obstacles=obs)
+            a, it, _, delta = refine_actions(cbf, s, a, idx, cfg.refine_loops, cfg.refine_lr, obstacles=obs, a_max=a_max,
+                                             return_delta=True)
             refine_iters += it
         with torch.no_grad():
+            if stats:
+                acts = merge_action_stats(acts, action_stats(a, delta, active, a_max))
             s = _euler(s, a)
             safe = _safe_count(s, obs)
             safe_sum += float((safe * active.float()).sum())
@@ -273,6 +387,8 @@ def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dic
         mean_dist = float(d.mean())
     out = {"safety_rate": safe_sum / max(steps, 1), "reaching_rate": reach, "mean_goal_dist": mean_dist,
            "steps": t + 1, "agent_steps": steps, "refine_iters": refine_iters}
+    if stats:
+        out.update(action_metrics(dict(zip(ACTION_STATS, (int(x) for x in acts.tolist()))), steps, D))
     if cfg.diagnose:
         out["unsafe_agent_steps"] = float(unsafe_n)
         out["unsafe_pairs_in_topk_share"] = float(seen_n) / max(float(unsafe_n), 1.0)
@@ -296,6 +412,9 @@ def sample_scenarios(cfg: EvalConfig, episode: int, device):
                                 seed=cfg.seed * 7919 + episode)
 
 
+_MAX_KEYS = ("max_abs_action",)     # over the episodes: the maximum; every other key: the mean
+
+
 def evaluate(controller, cbf, cfg: EvalConfig, device: Optional[torch.device] = None) -> Dict[str, float]:
     """Run ``cfg.episodes`` fresh scenarios; returns metrics averaged over episodes."""
     device = device or next(controller.parameters()).device
@@ -307,6 +426,7 @@ def evaluate(controller, cbf, cfg: EvalConfig, device: Optional[torch.device] = 
     if cfg.dtype not in MFMA_DTYPES:
         raise ValueError(f"dtype must be one of {sorted(MFMA_DTYPES)}, got {cfg.dtype!r}")
     check_rollout_impl(cfg, device)
+    check_action_limit(cfg)
     if device.type == "cuda":
         controller.mfma_dtype = cbf.mfma_dtype = MFMA_DTYPES[cfg.dtype]
     controller.eval()
@@ -317,5 +437,5 @@ def evaluate(controller, cbf, cfg: EvalConfig, device: Optional[torch.device] = 
         r = rollout_eval(controller, cbf, s0.to(device), g.to(device), cfg,
                          obstacles=None if obs is None else obs.to(device))
         for kk, v in r.items():
-            agg[kk] = agg.get(kk, 0.0) + float(v)
-    return {kk: v / cfg.episodes for kk, v in agg.items()}
+            agg[kk] = max(agg.get(kk, 0.0), float(v)) if kk in _MAX_KEYS else agg.get(kk, 0.0) + float(v)
+    return {kk: v if kk in _MAX_KEYS else v / cfg.episodes for kk, v in agg.items()}

@@ -19,6 +19,12 @@ its expressions, ``a32 + delta`` and ``s + [v, u] * dt``, in fp32 without contra
 decision compares an integer sum of per-agent distances (2^-32 fixed point) with the threshold
 instead of an fp32 mean: the two can differ only for a mean within summation error (about
 N * 2^-24 of its value) of ``DIST_MIN_CHECK``.
+
+``a_max`` (opt-in) is the per-axis actuator limit of ``evaluate.py``'s module docstring: after the
+controller forward ``episode_limit_kernel`` clamps the actions in place, the filter projects its
+correction, and the Euler step applies clamp(a_c + delta). ``action_stats`` adds the integer action
+statistics (``evaluate.ACTION_STATS``), accumulated by the Euler step's kernel over the agents of the
+envs that are active at the start of each step.
 """
 from __future__ import annotations
 
@@ -33,12 +39,14 @@ from .refine import choose_impl
 
 def run_episodes(controller, cbf, s0, g, obstacles=None, *, refine, loops=C.REFINE_LOOPS,
                  lr=C.REFINE_LEARNING_RATE, max_steps=C.INNER_LOOPS, top_k=C.TOP_K, mask_done=True, check_every=5,
-                 impl=None, return_state=False):
+                 impl=None, return_state=False, a_max=None, action_stats=False):
     """s0 (B, N, 2D), g (B, N, D) on the HIP device, obstacles (B, M, D) or None -> the batch's totals,
     an int64 device vector in the order of ``validate.COUNTS``; with ``return_state`` also the final
     states (B, N, 2D) and the final ``active`` (B,) bool. ``impl``: the filter's implementation
     (None / "loop" / "persistent", ``ops.refine``). Nothing is read on the host except the driver's
-    flag; the caller decides when to read the vector."""
+    flag; the caller decides when to read the vector. ``a_max``: the actuator limit (module docstring);
+    ``action_stats=True`` appends one more element to the result, the int64 device vector of
+    ``evaluate.ACTION_STATS``."""
     if not isinstance(s0, torch.Tensor) or not s0.is_cuda:
         raise native.NativeError("run_episodes runs on the HIP device")
     if s0.dim() != 3 or g.dim() != 3 or s0.shape[-1] not in (4, 6) or g.shape != (*s0.shape[:2], s0.shape[-1] // 2):
@@ -49,6 +57,8 @@ def run_episodes(controller, cbf, s0, g, obstacles=None, *, refine, loops=C.REFI
     if K > C.MAX_TOP_K:
         raise native.NativeError(f"K = {K} neighbour slots, the kernels take at most MAX_TOP_K = {C.MAX_TOP_K}")
     loops, max_steps = int(loops), int(max_steps)
+    if a_max is not None:                       # the fp32 value the kernels compare with
+        a_max = float(torch.tensor(native._a_max(a_max), dtype=torch.float32))
     dev = s0.device
     cmp_ = module_pack("ctrl", controller, dev)
     bmp = None
@@ -88,6 +98,8 @@ def run_episodes(controller, cbf, s0, g, obstacles=None, *, refine, loops=C.REFI
                    dist_fx=torch.zeros(B, **i64), safe=torch.zeros(B, dtype=torch.float32, device=dev),
                    active=torch.ones(B, dtype=torch.uint8, device=dev),
                    prev_active=torch.zeros(B, dtype=torch.uint8, device=dev), out=torch.empty(native.EP_OUT, **i64))
+        if action_stats:
+            buf.update(act_st=torch.zeros(native.EP_ACT_WORDS, **i64), act_out=torch.empty(native.EP_ACT_WORDS, **i64))
         if filt:
             buf.update(delta=torch.zeros(B, N, D, dtype=torch.float32, device=dev),
                        h=torch.empty(B, N, K, dtype=torch.float32, device=dev),
@@ -100,9 +112,11 @@ def run_episodes(controller, cbf, s0, g, obstacles=None, *, refine, loops=C.REFI
                 buf["dEv"] = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
         _, cur = native.episode_run(buf, K=K, max_steps=max_steps, check_every=check_every, refine=refine, loops=loops,
                                     lr=lr, mask_done=mask_done, persistent=persistent, ctrl=(cw, cv, crm, cmp_),
-                                    cbf=(bw, bv, brm, bmp) if refine else None)
-        out = buf["out"]
-        if not return_state:
-            return out
-        s_fin = native.from_records(buf["S1" if cur else "S0"][:, :N]).to(s0.dtype).contiguous()
-        return out, s_fin, buf["active"].bool()
+                                    cbf=(bw, bv, brm, bmp) if refine else None, a_max=a_max)
+        res = (buf["out"],)
+        if return_state:
+            s_fin = native.from_records(buf["S1" if cur else "S0"][:, :N]).to(s0.dtype).contiguous()
+            res += (s_fin, buf["active"].bool())
+        if action_stats:
+            res += (buf["act_out"],)
+        return res if len(res) > 1 else res[0]

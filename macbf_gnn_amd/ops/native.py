@@ -874,8 +874,18 @@ def refine_grid(E: int, device, prec_code: int) -> int:
     return max(1, min((tiles + waves - 1) // waves, num_cu(device)))
 
 
+def _a_max(a_max) -> float:
+    """The actuator limit as the kernels take it: 0.0 is off."""
+    if a_max is None:
+        return 0.0
+    a_max = float(a_max)
+    if not (0.0 < a_max < float("inf")):
+        raise NativeError(f"a_max must be a positive finite number or None, got {a_max!r}")
+    return a_max
+
+
 def _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec, hn_out, flag_out,
-                 env_active, lr):
+                 env_active, lr, a_max=None):
     """The argument validation shared by ``refine`` and ``refine_small`` ->
     (B, N, Nn, K, D, loops, precision code, the RefineArgs fields of ``_refine_kw``)."""
     if S is None or S.dim() != 3:
@@ -923,12 +933,15 @@ def _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loo
         if env_active.dtype == torch.bool:
             env_active = env_active.view(torch.uint8)         # same bytes, 0 / 1
     return B, N, Nn, K, D, loops, code, _refine_kw(B, N, Nn, K, D, S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr,
-                                                   redges, lr, hn_out, flag_out, env_active)
+                                                   redges, lr, hn_out, flag_out, env_active, a_max=a_max)
 
 
 def _refine_kw(B, N, Nn, K, D, S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, lr, hn_out=None,
-               flag_out=None, env_active=None, **loop):
-    """The RefineArgs fields (csrc/args.h) both filters take; `loop`: what the caller adds (dEv, ctl, launch parameters)."""
+               flag_out=None, env_active=None, a_max=None, **loop):
+    """The RefineArgs fields (csrc/args.h) both filters take; `loop`: what the caller adds (dEv, ctl, launch
+    parameters). The actuator limit is an optional key of the native layer: passed only when one is set."""
+    if _a_max(a_max) > 0.0:
+        loop["a_max"] = _a_max(a_max)
     return dict(S=ptr(S), s_env=Nn, dim=D, idx=ptr(idx), a=ptr(a), delta=ptr(delta), h=ptr(h), B=B, N=N, Nn=Nn, K=K,
                 wpack=ptr(wpack), f_bwd=int(f_bwd), wrm=ptr(wrm), wvec=ptr(wvec), ptr=ptr(rptr), edges=ptr(redges),
                 dt=float(C.TIME_STEP), dt_alpha=float(C.TIME_STEP * C.ALPHA_CBF), lr=float(lr), hn_out=ptr(hn_out),
@@ -937,7 +950,7 @@ def _refine_kw(B, N, Nn, K, D, S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rpt
 
 
 def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl, *, loops, lr,
-           prec=None, hn_out=None, flag_out=None, num_blocks=None, env_active=None):
+           prec=None, hn_out=None, flag_out=None, num_blocks=None, env_active=None, a_max=None):
     """The safety-filter loop (csrc/refine.hip + the driver in csrc/runtime.cpp): ``loops`` gradient
     steps of ``delta`` (B, N, D), in place, on sum_e relu(-(h(s') - h + dt alpha h)) with
     s' = s + dt [v, a + delta].
@@ -951,12 +964,13 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
     (optional): h(s') and the hinge flags of the first iteration. env_active (B,) bool / uint8 on the
     device (optional): envs with 0 are left out -- their delta stays zero, they write no dEv / trace
     and ctl counts the other envs alone; None is every env. The mask is read by the kernels only.
-    No host synchronisation.
+    a_max (optional): the per-axis actuator limit -- ``a`` must already be clamped to [-a_max, a_max];
+    every update then projects delta onto [-a_max - a, a_max - a]. No host synchronisation.
     fp32 (x3) and bf16 builds; fp16 is not supported (the -1 upstream gradient has no loss scaling)."""
     if dEv is None or ctl is None:
         raise NativeError("dEv and ctl are required")
     B, N, Nn, K, D, loops, code, kw = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec,
-                                                   hn_out, flag_out, env_active, lr)
+                                                   hn_out, flag_out, env_active, lr, a_max)
     check(dEv, torch.float32, (B, N, K, D), "dEv")
     check(ctl, torch.int64, None, "ctl")
     if ctl.dim() != 1 or ctl.numel() < 2 * loops:
@@ -979,7 +993,7 @@ def refine_small_eligible(Nn: int, K: int) -> bool:
 
 
 def refine_small(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, ew, *, loops, lr,
-                 prec=None, hn_out=None, flag_out=None, env_active=None):
+                 prec=None, hn_out=None, flag_out=None, env_active=None, a_max=None):
     """The persistent safety filter of small envs (csrc/refine.hip refine_small_kernel): the whole
     loop of ``refine`` in ONE launch, one workgroup per env, for envs of at most SMALL_MAXN graph
     nodes. Arguments as for ``refine`` (no dEv: it lives in LDS), except the result words: ew
@@ -1003,7 +1017,7 @@ def refine_small(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, ew,
     if ew is None:
         raise NativeError("ew is required")
     B, N, Nn, K, D, loops, code, kw = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec,
-                                                   hn_out, flag_out, env_active, lr)
+                                                   hn_out, flag_out, env_active, lr, a_max)
     check(ew, torch.int64, (B, loops, 2), "ew")
     _ok(lib().refine_small(ew=ptr(ew), loops=loops, prec=code, stream=stream_handle(), **kw), "refine_small")
 
@@ -1428,6 +1442,7 @@ def stats_pack(sums, counts, local, row):
 # ----------------------------------------------------------------------------- closed-loop episodes
 EP_WORDS = 5                  # csrc/args.h: [alive, safe agent-steps, env steps, steps, filter iterations]
 EP_OUT = 8                    # result words, the order of validate.COUNTS
+EP_ACT_WORDS = 4              # action-statistic words, the order of evaluate.ACTION_STATS
 EP_MODES = {None: 0, "loop": 1, "persistent": 2}
 _EPISODE_DRIVER = None
 
@@ -1478,21 +1493,53 @@ def _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active):
                              ctl=0, ew=0, loops=0, mode=0, thr=float(C.DIST_MIN_CHECK), out=0)
 
 
-def episode_advance(S_cur, S_next, A, delta, G, st, dist_fx, safe, active, prev_active):
+def _episode_limit_kw(a_max, act_st=None, act_out=None) -> dict:
+    """The optional EpisodeArgs keys: passed only when a limit is set / the statistics are asked for."""
+    kw = {}
+    if _a_max(a_max) > 0.0:
+        kw["a_max"] = _a_max(a_max)
+    if act_st is not None:
+        kw["act_st"] = ptr(act_st)
+    if act_out is not None:
+        kw["act_out"] = ptr(act_out)
+    return kw
+
+
+def episode_limit(A, a_max):
+    """The controller's actions clamped to the actuator box, in place (csrc/episode.hip
+    episode_limit_kernel, one thread per component): A (B, N, D) float32 <- clamp(A, -a_max, a_max)."""
+    if not isinstance(A, torch.Tensor) or A.dim() != 3 or A.shape[-1] not in (2, 3):
+        raise NativeError("A must be float32 (B, N, D) with D = 2 or 3")
+    B, N, D = A.shape
+    _ep(A, torch.float32, (B, N, D), "A")
+    if _a_max(a_max) <= 0.0:
+        raise NativeError("episode_limit needs a limit: a_max must be a positive finite number")
+    _ep_device(A=A)
+    _ok(lib().episode_limit(S_cur=0, S_next=0, s_env=N, dim=D, B=B, N=N, A=ptr(A), delta=0, G=0, dt=0.0, st=0, dist_fx=0,
+                            safe=0, active=0, prev_active=0, ctl=0, ew=0, loops=0, mode=0, thr=0.0, out=0,
+                            a_max=_a_max(a_max), stream=stream_handle()), "episode_limit")
+
+
+def episode_advance(S_cur, S_next, A, delta, G, st, dist_fx, safe, active, prev_active, *, a_max=None, act_st=None):
     """One Euler step of every agent (csrc/episode.hip episode_advance_kernel): S_next's agent records
-    = s + [v, A + delta] * dt of S_cur's (unchanged when st[0], the "some env still runs" word, is 0),
-    dist_fx[b] += sum_i |p'_i - g_i| * FX_DIST. S_cur / S_next (B, Nn, 4|8) distinct record buffers
-    (obstacle rows are not touched); A (B, N, D); delta (B, N, D) or None, zeroed once it is read."""
+    = s + [v, u] * dt of S_cur's with u = A + delta (unchanged when st[0], the "some env still runs" word,
+    is 0), dist_fx[b] += sum_i |p'_i - g_i| * FX_DIST. S_cur / S_next (B, Nn, 4|8) distinct record buffers
+    (obstacle rows are not touched); A (B, N, D); delta (B, N, D) or None, zeroed once it is read.
+    a_max (optional): u is clamped to [-a_max, a_max]. act_st (EP_ACT_WORDS,) int64 (optional): the
+    running action statistics (evaluate.ACTION_STATS) gain this step's, over the agents of the envs
+    with active != 0."""
     B, N, Nn, D, kw = _episode_state(S_cur, G, st, dist_fx, safe, active, prev_active)
     _ep(S_next, torch.float32, tuple(S_cur.shape), "S_next")
     _ep(A, torch.float32, (B, N, D), "A")
     _ep(delta, torch.float32, (B, N, D), "delta", required=False)
+    _ep(act_st, torch.int64, (EP_ACT_WORDS,), "act_st", required=False)
     if S_next.data_ptr() == S_cur.data_ptr():
         raise NativeError("S_next must not be S_cur")
     _ep_device(S_cur=S_cur, S_next=S_next, A=A, delta=delta, G=G, st=st, dist_fx=dist_fx, safe=safe, active=active,
-               prev_active=prev_active)
+               prev_active=prev_active, act_st=act_st)
     _ok(lib().episode_advance(S_cur=ptr(S_cur), S_next=ptr(S_next), stream=stream_handle(),
-                              **dict(kw, A=ptr(A), delta=ptr(delta))), "episode_advance")
+                              **dict(kw, A=ptr(A), delta=ptr(delta)), **_episode_limit_kw(a_max, act_st)),
+        "episode_advance")
 
 
 def _episode_words(B, ctl, ew, loops):
@@ -1534,7 +1581,8 @@ def episode_final(S_cur, G, st, dist_fx, safe, active, prev_active, out):
     _ok(lib().episode_final(S_cur=ptr(S_cur), S_next=0, stream=stream_handle(), **dict(kw, out=ptr(out))), "episode_final")
 
 
-def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask_done, persistent, ctrl, cbf):
+def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask_done, persistent, ctrl, cbf,
+                a_max=None):
     """A whole batch of closed-loop episodes as one native call (csrc/runtime.cpp EpisodeDriver).
 
     buf: the call's device buffers (ops/episode.py allocates them): S0 / S1 (B, Nn, 4|8) record
@@ -1544,7 +1592,10 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     prev_active (B,) uint8 zero; out (EP_OUT,) int64; with refine and loops > 0 also delta (B, N, D)
     zero, h (B, N, K), rptr (B, Nn+1) / redges (B, N*K) int32 and ctl (2*loops,) int64 + dEv
     (B, N, K, D) (loop filter) or ew (B, loops, 2) int64 zero (persistent). ctrl / cbf: (wpack, wvec,
-    wrm, ModulePack) of the packed networks (cbf may be None without refine).
+    wrm, ModulePack) of the packed networks (cbf may be None without refine). a_max (optional): the
+    per-axis actuator limit (the controller's actions are clamped in place, the filter projects, the
+    applied action is clamped). buf may hold act_st (EP_ACT_WORDS,) int64 zero and act_out
+    (EP_ACT_WORDS,) int64, both or neither: the action statistics (evaluate.ACTION_STATS).
     Returns (steps issued, index of the record buffer that holds the final state)."""
     K, max_steps, check_every, loops = int(K), int(max_steps), int(check_every), int(loops)
     if K < 1 or K > C.MAX_TOP_K:
@@ -1577,6 +1628,11 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     _ep(buf.get("A"), torch.float32, (B, N, D), "A")
     _ep(buf.get("perm"), torch.int32, (B, Nn), "perm")
     _ep(buf.get("out"), torch.int64, (EP_OUT,), "out")
+    if (buf.get("act_st") is None) != (buf.get("act_out") is None):
+        raise NativeError("act_st and act_out come together")
+    _ep(buf.get("act_st"), torch.int64, (EP_ACT_WORDS,), "act_st", required=False)
+    _ep(buf.get("act_out"), torch.int64, (EP_ACT_WORDS,), "act_out", required=False)
+    limit_kw = _episode_limit_kw(a_max, buf.get("act_st"), buf.get("act_out"))
     cw, cv, _, cmp_ = ctrl
     pc = _half(cw, "controller wpack", cmp_.prec)
     _ep(cw, cw.dtype, tuple(cw.shape), "controller wpack")
@@ -1613,10 +1669,10 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     g = buf.get
     mode = EP_MODES[None if not filt else "persistent" if persistent else "loop"]
     ep.update(A=ptr(g("A")), delta=ptr(g("delta") if filt else None), ctl=ptr(g("ctl") if mode == 1 else None),
-              ew=ptr(g("ew") if mode == 2 else None), loops=loops, mode=mode, out=ptr(g("out")))
+              ew=ptr(g("ew") if mode == 2 else None), loops=loops, mode=mode, out=ptr(g("out")), **limit_kw)
     # the filter's arguments (S: per step; the mask is dropped by the driver unless mask_done)
     flt = _refine_kw(B, N, Nn, K, D, None, g("idx"), g("A"), g("delta"), g("h"), bw, bmp.off["w1f"], brm, bv, g("rptr"),
-                     g("redges"), lr, env_active=g("active"), dEv=ptr(g("dEv") if mode == 1 else None), ctl=ep["ctl"],
+                     g("redges"), lr, env_active=g("active"), a_max=a_max, dEv=ptr(g("dEv") if mode == 1 else None), ctl=ep["ctl"],
                      ew=ep["ew"], loops=loops, num_blocks=refine_grid(E, dev, qc), prec=qc) if filt else None
     # the step's launches on S0 (the driver swaps the record buffers): one scan with the kNN lists and the
     # safety count, the safety-only scan of the final state, the controller, and the filter's h(s_t) and CSR

@@ -23,6 +23,11 @@ stops on its own and reports per-env result words, which ``native.refine_reduce`
 loop path's ``used`` / ``viol`` / counts on the device. ``impl=None`` chooses: ``MACBF_REFINE_SMALL``
 (0 / 1) if set, else the persistent kernel where it measured faster (``AUTO_PERSISTENT``: bf16 envs
 of at most 32 graph nodes; docs/PERF.md, "Persistent filter") and the loop everywhere else.
+
+``a_max`` (opt-in): the per-axis actuator limit of ``evaluate.py``'s module docstring. The action is
+clamped with a torch op before the launches, both update kernels project ``delta`` onto
+[-a_max - a_c, a_max - a_c] after every step (behind one scalar test: without a limit they run the
+instructions they always ran), and the result is clamp(a_c + delta, -a_max, a_max).
 """
 from __future__ import annotations
 
@@ -30,6 +35,7 @@ import torch
 
 from .. import config as C
 from .. import knobs
+from ..evaluate import check_a_max
 from . import graph, native
 from .packing import module_pack
 
@@ -61,14 +67,17 @@ def choose_impl(impl, prec: str, Nn: int, K: int) -> str:
 
 def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_LOOPS,
                   lr: float = C.REFINE_LEARNING_RATE, return_trace: bool = False, *, env_active=None,
-                  num_blocks=None, impl=None):
+                  num_blocks=None, impl=None, a_max=None, return_delta: bool = False):
     """s (B, N, 2D), a (B, N, D), idx (B, N, K) on the HIP device, obstacles (B, M, D) or None ->
     (a_refined (B, N, D), used, viol); ``used`` (int64) and ``viol`` (float64) are 0-d device
     tensors -- the caller decides when to read them. ``return_trace=True`` appends a dict with the
     per-iteration active-edge counts ``counts`` (loops,), and ``hn`` (B, N, K) / ``active`` (B, N, K)
     bool of the first iteration (tests). ``env_active`` (B,): envs with False / 0 are not refined
     (module docstring); ``num_blocks`` overrides the workgroup count of the loop path's gradient
-    kernel; ``impl`` None / "loop" / "persistent" (module docstring)."""
+    kernel; ``impl`` None / "loop" / "persistent" (module docstring). ``a_max``: the actuator limit
+    (module docstring); the trace dict also holds the raw ``delta`` (B, N, D), and ``return_delta=True``
+    appends it as a last element of its own."""
+    a_max = check_a_max(a_max)
     if not s.is_cuda:
         raise native.NativeError("the safety filter runs on the HIP device")
     if s.dim() != 3 or a.dim() != 3 or idx.dim() != 3:
@@ -94,6 +103,8 @@ def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_L
         Nn = S.shape[1]
         idx32 = idx.to(torch.int32).contiguous()
         a32 = a.detach().float().contiguous()
+        if a_max is not None:
+            a32 = a32.clamp(-a_max, a_max)
         delta = torch.zeros_like(a32)
         h = torch.empty(1, B, N, K, dtype=torch.float32, device=dev)
         persistent = choose_impl(impl, mp.prec, Nn, K) == "persistent"
@@ -115,12 +126,12 @@ def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_L
             if persistent:
                 native.refine_small(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, rptr, redges, ew,
                                     loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags,
-                                    env_active=env_active)
+                                    env_active=env_active, a_max=a_max)
             else:
                 dEv = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
                 native.refine(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, dEv, rptr, redges, ctl,
                               loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags, env_active=env_active,
-                              num_blocks=num_blocks)
+                              num_blocks=num_blocks, a_max=a_max)
         if persistent:
             used, viol, counts = native.refine_reduce(ew)
         else:
@@ -133,7 +144,12 @@ def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_L
                 viol = ctl[1:2 * loops:2].index_select(0, last).view(()).double() / native.FX_VIOL
             else:
                 viol = torch.zeros((), dtype=torch.float64, device=dev)
-        out = (a32 + delta).to(a.dtype)
+        out = a32 + delta
+        if a_max is not None:
+            out = out.clamp(-a_max, a_max)
+        out = out.to(a.dtype)
+    res = (out, used, viol)
     if return_trace:
-        return out, used, viol, {"counts": counts.clone(), "hn": hn, "active": flags.bool() if flags is not None else None}
-    return out, used, viol
+        res += ({"counts": counts.clone(), "hn": hn, "active": flags.bool() if flags is not None else None,
+                 "delta": delta},)
+    return res + (delta,) if return_delta else res

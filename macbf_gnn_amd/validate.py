@@ -25,6 +25,13 @@ opt-in) runs each rollout as one native call, ``ops.episode.run_episodes(..., ma
 the same count vector, so everything after ``rollout()`` is shared. ``"python"`` stays the default
 and the reference.
 
+``val_a_max > 0`` (``TrainConfig.val_a_max``, ``train.py --val_a_max``; 0: off) puts the per-axis
+actuator limit of ``evaluate.py``'s module docstring on both rollouts: the nominal action is clamped,
+the filter projects, and the dict gains ``val_limited_rate``, ``val_refined_limited_rate``,
+``val_refined_intervention_rate`` and ``val_refined_mean_abs_delta``. Their three integer sums
+(``ACTION_SUMS``) travel in the same all-reduce, after the existing counts; the largest |u| is left
+out (it would need a second reduction of another kind). Training rollouts are not touched.
+
 Precision (HIP): the networks run at the training ``dtype``. The filter has no fp16 build (its -1
 upstream gradient has no loss scaling), so a run that trains in fp16 validates both networks in
 bf16. ``validate`` puts ``mfma_dtype`` and the train / eval mode of both modules back, draws from
@@ -38,13 +45,15 @@ from typing import Dict, Optional
 import torch
 
 from . import config as C
-from .evaluate import MFMA_DTYPES, _euler, _knn, _safe_count, refine_actions
+from .evaluate import (ACTION_STATS, DELTA_FX, MFMA_DTYPES, _euler, _knn, _safe_count, action_stats, check_a_max,
+                       refine_actions)
 
 VAL_SALT = 0x56414C5345454453          # the validation scenes' seed stream: _mix(cfg.seed, VAL_SALT)
 CHECK_EVERY = 5                        # rollout steps between host reads of the "all done" flag
 DIST_FX = float(1 << 20)               # fixed-point scale of the goal-distance sum
 COUNTS = ("safe_agent_steps", "agent_steps", "reached_agents", "agents", "env_steps", "refine_iters", "steps",
           "goal_dist_fx")
+ACTION_SUMS = ACTION_STATS[:3]         # with val_a_max: the integer sums that follow COUNTS in a rollout's vector
 RATE_KEYS = ("val_safety_rate", "val_reaching_rate", "val_refined_safety_rate", "val_refined_reaching_rate")
 _UNSET = object()
 
@@ -66,6 +75,12 @@ def check_config(cfg, device=None):
     if impl == "native" and on_cpu:
         raise ValueError("val_impl='native' runs the validation rollouts as native HIP episodes (ops/episode.py): it "
                          "needs a HIP device; use val_impl='python' on CPU")
+    a_max = getattr(cfg, "val_a_max", 0.0)
+    if a_max != 0.0:
+        try:
+            check_a_max(a_max)
+        except ValueError as e:
+            raise ValueError(f"val_a_max must be a positive finite number, or 0 for no limit: {e}") from None
     if cfg.val_every < 0 or cfg.val_envs < 1 or cfg.val_refine_loops < 0:
         raise ValueError("val_every must be >= 0, val_envs >= 1 and val_refine_loops >= 0")
     m = default_best_metric(cfg)
@@ -85,9 +100,10 @@ def val_dtype(cfg) -> torch.dtype:
     return torch.bfloat16 if cfg.dtype == "fp16" else MFMA_DTYPES[cfg.dtype]
 
 
-def metrics_from_counts(nom: Dict[str, int], ref: Optional[Dict[str, int]], num_agents: int) -> Dict[str, float]:
-    """The ``val_*`` ratios of the summed integer totals (``COUNTS``) of the nominal and, if it ran,
-    the filtered rollout."""
+def metrics_from_counts(nom: Dict[str, int], ref: Optional[Dict[str, int]], num_agents: int,
+                        dim: int = 2) -> Dict[str, float]:
+    """The ``val_*`` ratios of the summed integer totals (``COUNTS``, with an actuator limit also
+    ``ACTION_SUMS``) of the nominal and, if it ran, the filtered rollout."""
     envs = max(nom["agents"] // max(num_agents, 1), 1)
     out = {"val_safety_rate": nom["safe_agent_steps"] / max(nom["agent_steps"], 1),
            "val_reaching_rate": nom["reached_agents"] / max(nom["agents"], 1),
@@ -99,6 +115,13 @@ def metrics_from_counts(nom: Dict[str, int], ref: Optional[Dict[str, int]], num_
                     "val_refined_mean_T": ref["env_steps"] / envs,
                     # filter iterations per rollout step of a rank's batch
                     "val_refine_iters": ref["refine_iters"] / max(ref["steps"], 1)})
+    if "limited_agent_steps" in nom:
+        out["val_limited_rate"] = nom["limited_agent_steps"] / max(nom["agent_steps"], 1)
+        if ref is not None:
+            n = max(ref["agent_steps"], 1)
+            out.update({"val_refined_limited_rate": ref["limited_agent_steps"] / n,
+                        "val_refined_intervention_rate": ref["intervened_agent_steps"] / n,
+                        "val_refined_mean_abs_delta": ref["delta_abs_fx"] / DELTA_FX / (n * dim)})
     return out
 
 
@@ -121,6 +144,7 @@ class Validator:
         self.g = g.to(device).clone()
         self.obs = None if obs is None else obs.to(device).clone()
         self.max_steps = int(cfg.inner_loops)
+        self.a_max = check_a_max(getattr(cfg, "val_a_max", 0.0) or None)    # the fp32 limit, or None
         self.last_counts: Dict[str, Dict[str, int]] = {}      # the summed integer totals behind the last dict
 
     # ------------------------------------------------------------------ one rollout
@@ -128,26 +152,35 @@ class Validator:
         cfg = self.cfg
         if s.is_cuda:
             from .ops import refine as refine_ops
-            a, used, _ = refine_ops.safety_filter(cbf, s, a, idx, obstacles=self.obs, loops=cfg.val_refine_loops,
-                                                  lr=C.REFINE_LEARNING_RATE, env_active=active)
-            return a, used
+            a, used, _, delta = refine_ops.safety_filter(cbf, s, a, idx, obstacles=self.obs, loops=cfg.val_refine_loops,
+                                                         lr=C.REFINE_LEARNING_RATE, env_active=active, a_max=self.a_max,
+                                                         return_delta=True)
+            return a, used, delta
+        delta = torch.zeros_like(a)
         if not bool(active.any()):
-            return a, 0
-        ar, it, _ = refine_actions(cbf, s[active], a[active], idx[active], cfg.val_refine_loops,
-                                   C.REFINE_LEARNING_RATE, obstacles=None if self.obs is None else self.obs[active])
+            return a, 0, delta
+        ar, it, _, dr = refine_actions(cbf, s[active], a[active], idx[active], cfg.val_refine_loops,
+                                       C.REFINE_LEARNING_RATE, obstacles=None if self.obs is None else self.obs[active],
+                                       a_max=self.a_max, return_delta=True)
         a = a.clone()
         a[active] = ar
-        return a, it
+        delta[active] = dr
+        return a, it, delta
 
     def rollout(self, controller, cbf, refine: bool) -> torch.Tensor:
         """One batch of episodes from the fixed scenes -> this rank's totals, an int64 device vector
-        in the order of ``COUNTS``. No host read except the "all done" flag every CHECK_EVERY steps."""
+        in the order of ``COUNTS``, with an actuator limit followed by ``ACTION_SUMS``. No host read
+        except the "all done" flag every CHECK_EVERY steps."""
         s, g, obs = self.s0, self.g, self.obs
+        a_max = self.a_max
         if self.impl == "native":
             from .ops import episode
-            return episode.run_episodes(controller, cbf, s, g, obs, refine=refine, loops=self.cfg.val_refine_loops,
-                                        lr=C.REFINE_LEARNING_RATE, max_steps=self.max_steps, top_k=self.cfg.top_k,
-                                        mask_done=True, check_every=CHECK_EVERY)
+            kw = dict(refine=refine, loops=self.cfg.val_refine_loops, lr=C.REFINE_LEARNING_RATE, max_steps=self.max_steps,
+                      top_k=self.cfg.top_k, mask_done=True, check_every=CHECK_EVERY)
+            if a_max is None:
+                return episode.run_episodes(controller, cbf, s, g, obs, **kw)
+            vec, acts = episode.run_episodes(controller, cbf, s, g, obs, a_max=a_max, action_stats=True, **kw)
+            return torch.cat([vec, acts[:len(ACTION_SUMS)]])
         B, N, _ = s.shape
         D = s.shape[-1] // 2
         k = min(self.cfg.top_k, N)
@@ -155,15 +188,21 @@ class Validator:
         zero = lambda: torch.zeros((), dtype=torch.int64, device=dev)
         safe_n, env_steps, iters, steps = zero(), zero(), zero(), zero()
         active = torch.ones(B, dtype=torch.bool, device=dev)
+        acts = None if a_max is None else torch.zeros(len(ACTION_SUMS), dtype=torch.int64, device=dev)
         for t in range(self.max_steps):
             alive = active.any()                     # device flag: false -> this step changes nothing
             idx = _knn(s, k, obs)
             with torch.no_grad():
                 a = controller(s, g, idx=idx, obstacles=obs)
+                if a_max is not None:
+                    a = a.clamp(-a_max, a_max)
+            delta = None
             if refine:
-                a, used = self._filter(cbf, s, a, idx, active)
+                a, used, delta = self._filter(cbf, s, a, idx, active)
                 iters += used
             with torch.no_grad():
+                if a_max is not None:
+                    acts += action_stats(a, delta, active, a_max)[:len(ACTION_SUMS)]
                 s = torch.where(alive, _euler(s, a), s)
                 act = active.long()
                 safe_n += (_safe_count(s, obs).long() * act).sum()
@@ -178,7 +217,8 @@ class Validator:
             reached = (d < C.DIST_MIN_CHECK).sum()
             dist_fx = (d.double().sum() * DIST_FX).round().long()
             agents = torch.full((), B * N, dtype=torch.int64, device=dev)
-            return torch.stack([safe_n, env_steps * N, reached, agents, env_steps, iters, steps, dist_fx])
+            vec = torch.stack([safe_n, env_steps * N, reached, agents, env_steps, iters, steps, dist_fx])
+            return vec if a_max is None else torch.cat([vec, acts])
 
     # ------------------------------------------------------------------ both rollouts, all ranks
     def _reduce(self, vec: torch.Tensor):
@@ -213,12 +253,20 @@ class Validator:
                     m.__dict__.pop("mfma_dtype", None)
                 else:
                     m.mfma_dtype = dt
-        tot = self._reduce(torch.cat(vecs))          # one collective, one host read
         n = len(COUNTS)
+        # the existing counts of every rollout first, in their places; the action sums after them
+        if self.a_max is not None:
+            vecs = [v[:n] for v in vecs] + [v[n:] for v in vecs]
+        tot = self._reduce(torch.cat(vecs))          # one collective, one host read
         nom = dict(zip(COUNTS, (int(x) for x in tot[:n])))
         ref = dict(zip(COUNTS, (int(x) for x in tot[n:2 * n]))) if cfg.val_refine else None
+        if self.a_max is not None:
+            m, base = len(ACTION_SUMS), n * (len(vecs) // 2)
+            nom.update(zip(ACTION_SUMS, (int(x) for x in tot[base:base + m])))
+            if ref is not None:
+                ref.update(zip(ACTION_SUMS, (int(x) for x in tot[base + m:base + 2 * m])))
         self.last_counts = {"nominal": nom} if ref is None else {"nominal": nom, "refined": ref}
-        out = metrics_from_counts(nom, ref, cfg.num_agents)
+        out = metrics_from_counts(nom, ref, cfg.num_agents, cfg.dim)
         out["val_ms"] = (time.perf_counter() - t0) * 1e3
         return out
 

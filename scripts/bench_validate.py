@@ -33,6 +33,9 @@ round, ``--rounds`` timed ones. Reports the minimum, the mean and the spread (ma
 difference of the minima, whether it exceeds the Python path's spread, and whether both gave the
 same counts.
 
+``--val_a_max A`` puts the actuator limit |u| <= A on the validation rollouts of every mode that
+runs ``validate()``.
+
 Prints one JSON line. Without ``--model_path`` the networks are random-initialised."""
 import argparse
 import json
@@ -86,6 +89,7 @@ def main():
     ap.add_argument("--model_path", type=str, default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--val_a_max", type=float, default=0.0, help="actuator limit of the validation rollouts (0: off)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(a.seed)
@@ -94,10 +98,12 @@ def main():
         ckpt.load_models(a.model_path, ctrl, cbf)
     cfg = C.TrainConfig(num_agents=a.num_agents, val_every=1, val_envs=a.val_envs, dim=a.dim, seed=a.seed,
                         num_obstacles=a.num_obstacles, dtype=a.dtype, val_refine_loops=a.refine_loops, device="hip")
+    if a.val_a_max:
+        cfg.val_a_max = a.val_a_max
     v = V.Validator(cfg, dev)
     out = {"mode": a.mode, "num_agents": a.num_agents, "val_envs": a.val_envs, "dim": a.dim,
            "num_obstacles": a.num_obstacles, "dtype": a.dtype, "refine_loops": a.refine_loops,
-           "model_path": a.model_path, "rounds": a.rounds}
+           "model_path": a.model_path, "rounds": a.rounds, "val_a_max": a.val_a_max}
     if a.mode == "validate":
         res = v.validate(ctrl, cbf)                      # warm-up
         ms = [v.validate(ctrl, cbf)["val_ms"] for _ in range(a.rounds)]
