@@ -127,3 +127,69 @@ def test_grad_assemble_check_and_stats_row():
         assert torch.equal(grad, g0)
         assert int(ok) == (0 if poison else 1)
         assert torch.equal(row, ref_row)
+
+
+@pytest.mark.parametrize("with_gscale", [False, True])
+def test_grad_assemble_ragged_csr_equals_float64_sum(with_gscale):
+    """Segments of length 0 / 1 / 2 / 7 / 300 over a source list with repeats, against a float64 sum.
+    The kernel adds a segment's len terms one after the other in fp32 (the first addition, to 0, is
+    exact: len - 1 roundings) and multiplies by the scale (one more):
+    |err| <= (max(len - 1, 1) + 1) * 2**-24 * scale * sum|terms|; an empty segment gives exactly 0.
+    The device loss scale is a power of two, so scale / gscale is exact."""
+    g = torch.Generator().manual_seed(21)
+    n, nred = 601, 5000
+    lens = torch.tensor([0, 1, 2, 7, 300])[torch.randint(0, 5, (n,), generator=g)]
+    lens[:5] = torch.tensor([0, 1, 2, 7, 300])
+    ptr = torch.zeros(n + 1, dtype=torch.int64)
+    ptr[1:] = lens.cumsum(0)
+    src = torch.randint(0, nred, (int(ptr[-1]),), generator=g)
+    assert src.unique().numel() < src.numel()                   # repeats
+    red = torch.randn(nred, generator=g)
+    scale = 0.3
+    gs = torch.tensor([1024.0], device=DEV) if with_gscale else None
+    grad = torch.full((n,), 99.0, device=DEV)
+    native.grad_assemble(red.to(DEV), ptr.to(torch.int32).to(DEV), src.to(torch.int32).to(DEV), grad, scale=scale,
+                         gscale=gs)
+    torch.cuda.synchronize()
+    s64 = float(torch.tensor(scale, dtype=torch.float32)) / (1024.0 if with_gscale else 1.0)
+    terms = red.double()[src]
+    seg = torch.repeat_interleave(torch.arange(n), lens)
+    want = torch.zeros(n, dtype=torch.float64).index_add_(0, seg, terms) * s64
+    asum = torch.zeros(n, dtype=torch.float64).index_add_(0, seg, terms.abs())
+    bound = ((lens - 1).clamp_min(1) + 1).double() * 2.0 ** -24 * s64 * asum
+    err = (grad.cpu().double() - want).abs()
+    print(f"RATIO grad_assemble {float((err[bound > 0] / bound[bound > 0]).max()):.4f}")
+    assert bool((err <= bound).all()), float((err - bound).max())
+    assert bool((grad.cpu()[lens == 0] == 0).all()) and int((lens == 0).sum()) > 0
+
+
+@pytest.mark.parametrize("f16", [False, True])
+def test_pack_gather_real_index_maps(f16):
+    """Random maps with repeats, the constant entries n (0) and n + 1 (1), and bit 30 on some 16-bit
+    indices (bf16: the residual bf16(v - float(bf16(v))); fp16 ignores the bit): exact against torch
+    casts. m16 + m32 is no multiple of the block size."""
+    g = torch.Generator().manual_seed(22)
+    n, m16, m32 = 1000, 300, 213
+    assert (m16 + m32) % 256 != 0
+    src = torch.randn(n, generator=g)
+    ext = torch.cat([src, torch.tensor([0.0, 1.0])])
+    k16 = torch.randint(0, n + 2, (m16,), generator=g)
+    k16[:4] = torch.tensor([n, n + 1, n, n + 1])
+    lo = torch.rand(m16, generator=g) < 0.3
+    lo[:2], lo[2:4] = False, True
+    k32 = torch.randint(0, n + 2, (m32,), generator=g)
+    k32[-2:] = torch.tensor([n, n + 1])
+    idx16 = (k16 + lo.long() * (1 << 30)).to(torch.int32).to(DEV)
+    out16 = torch.zeros(m16, dtype=torch.float16 if f16 else torch.bfloat16, device=DEV)
+    out32 = torch.full((m32,), 99.0, device=DEV)
+    native.pack_gather(src.to(DEV), idx16, out16, k32.to(torch.int32).to(DEV), out32)
+    torch.cuda.synchronize()
+    v = ext[k16]
+    if f16:
+        want16 = v.half()
+    else:
+        hi = v.bfloat16()
+        want16 = torch.where(lo, (v - hi.float()).bfloat16(), hi)
+        assert bool((want16[lo] != hi[lo]).any())
+    assert torch.equal(out16.cpu().view(torch.int16), want16.view(torch.int16))
+    assert torch.equal(out32.cpu(), ext[k32])
