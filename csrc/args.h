@@ -94,6 +94,9 @@ struct CtrlArgs {
   // the node MLP's activations out, for the cooperative node backward to reuse instead of
   // recomputing them: agent (b,i) -> acts + (b*na_env + i) * NODE_ACT_BYTES (ctrl.hip), or null
   unsigned char* acts; long na_env;
+  // per-axis actuator limit of the training rollout (0: off): the Euler step applies
+  // clamp(a, -a_max, a_max); A, act_sum and the backward keep the raw action (oracle.py)
+  float a_max;
 };
 
 // Persistent small-scene rollout (ctrl.hip rollout_small_kernel): one workgroup per env runs
@@ -307,6 +310,9 @@ struct CtrlNodeBwdArgs {
   int coop;                            // set by the launchers: 32-agent chunks run node_bwd_coop
   unsigned long long* stamps;          // diagnostics (null in production): node_bwd_coop phase clocks,
                                        // [workgroup][wave][16] shader-clock values (scripts/stamps_node.py)
+  // the rollout's actuator limit (0: off): dL/da through the Euler step is zero where the raw
+  // action A lies outside [-a_max, a_max] or is NaN (state.h limit_adjoint)
+  float a_max;
 };
 
 // the cooperative 32-agent node backward (node_bwd_coop) runs every 32-agent chunk

@@ -295,7 +295,9 @@ DEV void edge_rel(const EdgeSt<D>& c, float (&rp)[D], float (&rv)[D]) {
 // step, per-env goal-distance and action-loss sums.
 // ACTS: the activations go to a.acts (a separate instantiation: the stores' registers would make
 // the fused x3 step kernel spill where they are not wanted)
-template <int D, bool ACTS, typename PoolFr>
+// LIM: the actuator limit (a.a_max != 0) is an instantiation of its own, so the limit-off kernels
+// are the code they were (docs/PERF.md)
+template <int D, bool ACTS, bool LIM, typename PoolFr>
 DEV void node_phase(const CtrlArgs& a, int g0, int APW, int total, PoolFr pool, const h16* wn, const float* nb2,
                     const float* nb3, const float* nb4, int lane) {
   const int r = lane & 31, h = lane >> 5;
@@ -359,10 +361,13 @@ DEV void node_phase(const CtrlArgs& a, int g0, int APW, int total, PoolFr pool, 
 #pragma unroll
       for (int q = 0; q < D; ++q) a.A[((long)b * a.a_env + i) * D + q] = av[q];
     }
+    // actuator limit (a_max != 0): the Euler step applies the clamped action; A, the action-loss
+    // term and the backward's mask keep the raw one (macbf_gnn_amd/oracle.py, "Actuator limit")
 #pragma unroll
     for (int q = 0; q < D; ++q) {
       snp[q] = sp[q] + sv[q] * a.dt;
-      snv[q] = sv[q] + av[q] * a.dt;
+      if constexpr (LIM) snv[q] = sv[q] + limit_action(av[q], a.a_max) * a.dt;
+      else snv[q] = sv[q] + av[q] * a.dt;
       ar[q] = -(ex[q] + a.sqrt3 * sv[q]);
     }
     if (a.Snext) store_rec<D>(a.Snext + (long)b * a.sn_env * REC<D>, (unsigned)i, snp, snv);
@@ -533,7 +538,7 @@ constexpr int CTRL_FWD_DENSE = 1;
 // 0 weight staging (from t0, the kernel start), 1 group prologue loads, per edge tile 2 load issue,
 // 3 edge features, 4 edge MLP, 5 pool + stores; 6 pooled-store wait, 7 node phase; 15 tile count
 // (scripts/stamps_ctrl.py). A separate instantiation: no runtime stamp branches in production.
-template <int D, bool SPLIT, bool GNODE = false, bool DENSE12 = false, bool ST = false, bool ACTS = false>
+template <int D, bool SPLIT, bool GNODE = false, bool DENSE12 = false, bool ST = false, bool ACTS = false, bool LIM = false>
 DEV void ctrl_fwd_groups(const CtrlArgs& a, const h16* wl, const h16* wn, const float* vl, h16* pools, int grp0,
                          int gstride, unsigned long long t0 = 0) {
   constexpr bool GPOOL = X3 || SPLIT;
@@ -668,7 +673,7 @@ DEV void ctrl_fwd_groups(const CtrlArgs& a, const h16* wl, const h16* wn, const 
       int bb, ii;
       agent_bi(ab, gi - g0, N, bb, ii);
       const h16* prow = a.pooled + (long)bb * a.p_env + (long)ii * PROW + 8 * h;
-      node_phase<D, ACTS>(a, g0, APW, total, [&](int kk) { return row_fr(prow + 16 * kk, 128); }, wn, nb2, nb3, nb4, lane);
+      node_phase<D, ACTS, LIM>(a, g0, APW, total, [&](int kk) { return row_fr(prow + 16 * kk, 128); }, wn, nb2, nb3, nb4, lane);
       stamp(7);
       continue;
     }
@@ -686,7 +691,7 @@ DEV void ctrl_fwd_groups(const CtrlArgs& a, const h16* wl, const h16* wn, const 
       }
     }
     // ---------------- node phase: lane column r = agent g0 + r
-    node_phase<D, ACTS>(a, g0, APW, total, [&](int kk) { return row_fr(pool + r * PSTR + 16 * kk + 8 * h, 0); },
+    node_phase<D, ACTS, LIM>(a, g0, APW, total, [&](int kk) { return row_fr(pool + r * PSTR + 16 * kk + 8 * h, 0); },
                   wn, nb2, nb3, nb4, lane);
     // the pool image is rewritten by the next group: finish all reads first
     lds_wave_sync();
@@ -750,7 +755,7 @@ DEV void publish_step(const CtrlArgs& a) {
 
 // FUSE (x3): all 72 fragments in LDS (145 KB) and the node phase of each group in the same
 // wave right after its edge phase (pooled rows through global memory): one launch per step.
-template <int WAVES, int D, bool FUSE, bool ST, bool ACTS>
+template <int WAVES, int D, bool FUSE, bool ST, bool ACTS, bool LIM = false>
 DEV void ctrl_fwd_body(const CtrlArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const unsigned long long t0 = ST ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -770,9 +775,9 @@ DEV void ctrl_fwd_body(const CtrlArgs& a) {
   const int nact = min((int)gridDim.x, (ngrp + WAVES - 1) / WAVES);
   const int lb = (ROLL_XCD && (int)blockIdx.x < nact) ? xcd_block((int)blockIdx.x, nact) : (int)blockIdx.x;
   if (CTRL_FWD_DENSE && a.K == 12 && apw % 8 == 0)
-    ctrl_fwd_groups<D, false, FUSE, true, ST, ACTS>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
+    ctrl_fwd_groups<D, false, FUSE, true, ST, ACTS, LIM>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
   else
-    ctrl_fwd_groups<D, false, FUSE, false, ST, ACTS>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
+    ctrl_fwd_groups<D, false, FUSE, false, ST, ACTS, LIM>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
   if constexpr (!X3 || FUSE) publish_step(a);   // the x3 split path publishes from its node kernel
 }
 
@@ -787,9 +792,16 @@ __global__ __launch_bounds__(WAVES * 64) void ctrl_fwd_acts_kernel(CtrlArgs a) {
   ctrl_fwd_body<WAVES, D, FUSE, false, true>(a);
 }
 
+// the same step under the actuator limit (a.a_max != 0; no phase clocks): a kernel of its own name,
+// the limit-off kernels keep theirs
+template <int WAVES, int D, bool FUSE, bool ACTS>
+__global__ __launch_bounds__(WAVES * 64) void ctrl_fwd_lim_kernel(CtrlArgs a) {
+  ctrl_fwd_body<WAVES, D, FUSE, false, ACTS, true>(a);
+}
+
 // Node phase of the controller step over the pooled rows in global memory, 32-agent groups
 // grp0, grp0 + gstride, ... (x3 steps, and the persistent small-scene rollout)
-template <int D, bool ACTS = false>
+template <int D, bool ACTS = false, bool LIM = false>
 DEV void ctrl_node_groups(const CtrlArgs& a, const h16* wn, const float* vl, int grp0, int gstride) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const int N = a.N;
@@ -799,7 +811,7 @@ DEV void ctrl_node_groups(const CtrlArgs& a, const h16* wn, const float* vl, int
     const int gi = min(g0 + r, total - 1);
     const int b = gi / N, i = gi - b * N;
     const h16* prow = a.pooled + (long)b * a.p_env + (long)i * PROW + 8 * h;
-    node_phase<D, ACTS>(a, g0, 32, total, [&](int kk) { return row_fr(prow + 16 * kk, 128); }, wn, vl + 128, vl + 256,
+    node_phase<D, ACTS, LIM>(a, g0, 32, total, [&](int kk) { return row_fr(prow + 16 * kk, 128); }, wn, vl + 128, vl + 256,
                   vl + 320, lane);
   }
 }
@@ -848,7 +860,15 @@ extern "C" int MB_SYM(ctrl_fwd)(const mb::CtrlArgs* a, int num_cu, hipStream_t s
     };
     // (4-wave workgroups for the slices' small grids -- one wave per SIMD on twice the CUs --
     // measured no faster: 8-env slice 2.825-2.833 vs 2.797-2.820 ms, profiles/r6b/)
-    if (a->dim == 3) {
+    if (a->a_max != 0.f) {
+      if (a->dim == 3) {
+        if (a->acts) go(ctrl_fwd_lim_kernel<CTRL_WAVES, 3, true, true>);
+        else go(ctrl_fwd_lim_kernel<CTRL_WAVES, 3, true, false>);
+      } else {
+        if (a->acts) go(ctrl_fwd_lim_kernel<CTRL_WAVES, 2, true, true>);
+        else go(ctrl_fwd_lim_kernel<CTRL_WAVES, 2, true, false>);
+      }
+    } else if (a->dim == 3) {
       if (a->stamps) go(ctrl_fwd_kernel<CTRL_WAVES, 3, true, true>);
       else if (a->acts) go(ctrl_fwd_acts_kernel<CTRL_WAVES, 3, true>);
       else go(ctrl_fwd_kernel<CTRL_WAVES, 3, true>);
@@ -864,7 +884,15 @@ extern "C" int MB_SYM(ctrl_fwd)(const mb::CtrlArgs* a, int num_cu, hipStream_t s
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(CTRL_WAVES * 64), lds, st, b);
   };
-  if (a->dim == 3) {
+  if (!X3 && a->a_max != 0.f) {
+    if (a->dim == 3) {
+      if (a->acts) go1(ctrl_fwd_lim_kernel<CTRL_WAVES, 3, false, true>);
+      else go1(ctrl_fwd_lim_kernel<CTRL_WAVES, 3, false, false>);
+    } else {
+      if (a->acts) go1(ctrl_fwd_lim_kernel<CTRL_WAVES, 2, false, true>);
+      else go1(ctrl_fwd_lim_kernel<CTRL_WAVES, 2, false, false>);
+    }
+  } else if (a->dim == 3) {
     if (a->acts) go1(ctrl_fwd_acts_kernel<CTRL_WAVES, 3>);
     else go1(ctrl_fwd_kernel<CTRL_WAVES, 3>);
   } else {
@@ -1035,7 +1063,9 @@ DEV void fused_combine(const CtrlNodeBwdArgs& a, bool ok, int b, int i, int h, f
 
 // Node backward over the chunks c0, c0 + cstride, ... of `a` (smem: the kernel's dynamic LDS;
 // P: this workgroup's slab row)
-template <int D>
+// LIM: the rollout's actuator limit (a.a_max != 0) is its own instantiation of the node-backward
+// kernels, so the limit-off kernels are the code they were (registers, schedule: docs/PERF.md)
+template <int D, bool LIM>
 DEV void node_bwd_body(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, long cstride, float* P) {
   constexpr int RM = (X3 ? 2 : 1) * NODE_RM_ELEMS;
   h16* wr = reinterpret_cast<h16*>(smem);
@@ -1178,6 +1208,7 @@ constexpr int NB_PREFETCH = 1;
       float da[D], ar[D];
 #pragma unroll
       for (int q = 0; q < D; ++q) { da[q] = a.dt * gnv[q]; ar[q] = -(ex[q] + a.sqrt3 * sv[q]); }
+      if constexpr (LIM) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
       float act_coef = a.act_scale ? a.act_coef / fmaxf(*a.act_scale, 1.f) : a.act_coef;
       if (a.gscale) act_coef *= *a.gscale;        // fp16: device loss scale
       if (vld && act_coef != 0.f) {
@@ -1430,7 +1461,7 @@ constexpr int NB_PREFETCH = 1;
 constexpr int NC_SW = 296;                           // 148 dwords: row reads spread over the banks
 static_assert(NC_SW * 32 <= NB_PL, "cooperative region must fit the stage plane");
 
-template <int D>
+template <int D, bool LIM>
 DEV void node_bwd_coop(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, long cstride, float* P) {
   constexpr int RM = (X3 ? 2 : 1) * NODE_RM_ELEMS;
   constexpr int SW = NC_SW, PLN = NB_PL;
@@ -1609,6 +1640,7 @@ DEV void node_bwd_coop(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, l
         float da[D], ar[D];
 #pragma unroll
         for (int q = 0; q < D; ++q) { da[q] = a.dt * gnv[q]; ar[q] = -(ex[q] + a.sqrt3 * sv[q]); }
+        if constexpr (LIM) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
         float act_coef = a.act_scale ? a.act_coef / fmaxf(*a.act_scale, 1.f) : a.act_coef;
         if (a.gscale) act_coef *= *a.gscale;
         if (vld && act_coef != 0.f) {
@@ -1794,14 +1826,25 @@ DEV void node_bwd_coop(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, l
 template <int D>
 __global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_node_bwd_kernel(CtrlNodeBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  node_bwd_body<D>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+  node_bwd_body<D, false>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+}
+// under the actuator limit: kernels of their own names, the limit-off kernels keep theirs
+template <int D>
+__global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_node_bwd_lim_kernel(CtrlNodeBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  node_bwd_body<D, true>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
 }
 
 // separate kernel: one shared body would size both paths' registers for the larger (spills)
 template <int D>
 __global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_node_bwd_coop_kernel(CtrlNodeBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  node_bwd_coop<D>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+  node_bwd_coop<D, false>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+}
+template <int D>
+__global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_node_bwd_coop_lim_kernel(CtrlNodeBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  node_bwd_coop<D, true>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2140,7 +2183,16 @@ static_assert(EB_WAVES == NB_WAVES, "the fused BPTT step runs both phases with o
 template <int D, int KC>
 __global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_bwd_step_kernel(CtrlNodeBwdArgs na, CtrlEdgeBwdArgs ea) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  node_bwd_coop<D>(na, smem, blockIdx.x, gridDim.x, na.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+  node_bwd_coop<D, false>(na, smem, blockIdx.x, gridDim.x, na.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this workgroup's dP / ego stores complete
+  __syncthreads();                                      // (and the node phase's LDS reads done)
+  edge_bwd_body<D, KC, true>(ea, smem, blockIdx.x, gridDim.x, ea.partial + (long)blockIdx.x * CTRL_EDGE_PARTIAL);
+}
+// the same step under the actuator limit (a kernel of its own name: the limit-off kernel keeps its own)
+template <int D, int KC>
+__global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_bwd_step_lim_kernel(CtrlNodeBwdArgs na, CtrlEdgeBwdArgs ea) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  node_bwd_coop<D, true>(na, smem, blockIdx.x, gridDim.x, na.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this workgroup's dP / ego stores complete
   __syncthreads();                                      // (and the node phase's LDS reads done)
   edge_bwd_body<D, KC, true>(ea, smem, blockIdx.x, gridDim.x, ea.partial + (long)blockIdx.x * CTRL_EDGE_PARTIAL);
@@ -2270,8 +2322,8 @@ DEV void small_scan(const RolloutSmallArgs& ra, const float4* Sb, int N, int Nn,
   }
 }
 
-template <int D, bool ACTS>
-__global__ __launch_bounds__(SR_WAVES * 64) void rollout_small_kernel(RolloutSmallArgs ra) {
+template <int D, bool ACTS, bool LIM>
+DEV void rollout_small_body(RolloutSmallArgs ra) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ SmallScanLds L;
   h16* wl = reinterpret_cast<h16*>(smem);                            // ew1f, ew2 (18 frags)
@@ -2357,7 +2409,7 @@ __global__ __launch_bounds__(SR_WAVES * 64) void rollout_small_kernel(RolloutSma
     stamp(1);
     __syncthreads();                                // the env's pooled rows -> node phase
     stamp(2);
-    ctrl_node_groups<D, ACTS>(e, wn, vl, wave, SR_WAVES);
+    ctrl_node_groups<D, ACTS, LIM>(e, wn, vl, wave, SR_WAVES);
     stamp(3);
     // s_{t+1} (read by this workgroup only) and the env's sum atomics (device scope) complete
     // before the barrier; the workgroup-scope barrier is enough for both
@@ -2396,6 +2448,16 @@ __global__ __launch_bounds__(SR_WAVES * 64) void rollout_small_kernel(RolloutSma
   }
 }
 
+template <int D, bool ACTS>
+__global__ __launch_bounds__(SR_WAVES * 64) void rollout_small_kernel(RolloutSmallArgs ra) {
+  rollout_small_body<D, ACTS, false>(ra);
+}
+// under the actuator limit (c.a_max != 0): a kernel of its own name, the limit-off kernel keeps its own
+template <int D, bool ACTS>
+__global__ __launch_bounds__(SR_WAVES * 64) void rollout_small_lim_kernel(RolloutSmallArgs ra) {
+  rollout_small_body<D, ACTS, true>(ra);
+}
+
 size_t rollout_small_lds() { return (size_t)CTRL_FWD_FRAGS * FRAG_SZ + CTRL_VEC * 4; }
 
 
@@ -2425,6 +2487,9 @@ extern "C" int MB_SYM(ctrl_node_bwd)(const mb::CtrlNodeBwdArgs* a, int num_block
   b.coop = node_bwd_coop_enabled() && a->chunk == 32;     // 32-agent chunks: the four waves cooperate
   const void* fn = a->dim == 3 ? (b.coop ? (const void*)ctrl_node_bwd_coop_kernel<3> : (const void*)ctrl_node_bwd_kernel<3>)
                                : (b.coop ? (const void*)ctrl_node_bwd_coop_kernel<2> : (const void*)ctrl_node_bwd_kernel<2>);
+  if (a->a_max != 0.f)      // the actuator limit: its own instantiations
+    fn = a->dim == 3 ? (b.coop ? (const void*)ctrl_node_bwd_coop_lim_kernel<3> : (const void*)ctrl_node_bwd_lim_kernel<3>)
+                     : (b.coop ? (const void*)ctrl_node_bwd_coop_lim_kernel<2> : (const void*)ctrl_node_bwd_lim_kernel<2>);
   (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   void* kargs[] = {&b};
   const hipError_t rc = hipLaunchKernel(fn, dim3(num_blocks), dim3(NB_WAVES * 64), kargs, lds, st);
@@ -2484,7 +2549,15 @@ extern "C" int MB_SYM(ctrl_bwd_step)(const mb::CtrlNodeBwdArgs* na, const mb::Ct
     hipLaunchKernelGGL(kern, dim3(num_blocks), dim3(NB_WAVES * 64), lds, st, n, e);
   };
   const bool k12 = ea->K == 12;
-  if (ea->dim == 3) {
+  if (na->a_max != 0.f) {      // the actuator limit: its own instantiations
+    if (ea->dim == 3) {
+      if (k12) go(ctrl_bwd_step_lim_kernel<3, 12>);
+      else go(ctrl_bwd_step_lim_kernel<3, 0>);
+    } else {
+      if (k12) go(ctrl_bwd_step_lim_kernel<2, 12>);
+      else go(ctrl_bwd_step_lim_kernel<2, 0>);
+    }
+  } else if (ea->dim == 3) {
     if (k12) go(ctrl_bwd_step_kernel<3, 12>);
     else go(ctrl_bwd_step_kernel<3, 0>);
   } else {
@@ -2506,7 +2579,15 @@ extern "C" int MB_SYM(rollout_small)(const mb::RolloutSmallArgs* a, hipStream_t 
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(c.B), dim3(SR_WAVES * 64), lds, st, *a);
   };
-  if (c.dim == 3) {
+  if (c.a_max != 0.f) {
+    if (c.dim == 3) {
+      if (c.acts) go(rollout_small_lim_kernel<3, true>);
+      else go(rollout_small_lim_kernel<3, false>);
+    } else {
+      if (c.acts) go(rollout_small_lim_kernel<2, true>);
+      else go(rollout_small_lim_kernel<2, false>);
+    }
+  } else if (c.dim == 3) {
     if (c.acts) go(rollout_small_kernel<3, true>);
     else go(rollout_small_kernel<3, false>);
   } else {

@@ -104,8 +104,16 @@ DEV Fr n16_w1T(const h16* W, int m0, int s, int lane) {
 
 // ST: phase clocks (diagnostics) in a separate instantiation (no runtime stamp branches in the
 // production kernel: see cbf16.h)
-template <int D, bool ST>
+// DL: the spatial dimension D (2, 3), plus N16_LIM for the instantiation that runs under the rollout's
+// actuator limit (a.a_max != 0). The limit is an instantiation of its own because a runtime test cost
+// the production fp32 kernel two more spilled registers (docs/PERF.md); it rides on the first
+// parameter because the limit-off kernels must stay the code, and keep the names (<D, ST>), they had:
+// a body shared by two kernels compiled to other register counts.
+constexpr int N16_LIM = 4;
+template <int DL, bool ST>
 __global__ __launch_bounds__(N16_NW * 64) void ctrl_node_bwd16_kernel(CtrlNodeBwdArgs a) {
+  constexpr int D = DL & 3;
+  constexpr bool LIM = (DL & N16_LIM) != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   h16* W1 = reinterpret_cast<h16*>(smem);
   float* vl = reinterpret_cast<float*>(smem + N16_LDS_W);
@@ -244,6 +252,7 @@ __global__ __launch_bounds__(N16_NW * 64) void ctrl_node_bwd16_kernel(CtrlNodeBw
       float da[D], ar[D];
 #pragma unroll
       for (int q = 0; q < D; ++q) { da[q] = a.dt * gnv[q]; ar[q] = -(ex[q] + a.sqrt3 * sv[q]); }
+      if constexpr (LIM) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
       float act_coef = a.act_scale ? a.act_coef / fmaxf(*a.act_scale, 1.f) : a.act_coef;
       if (a.gscale) act_coef *= *a.gscale;
       if (vld && act_coef != 0.f) {
@@ -527,7 +536,8 @@ static void launch_ctrl_node_bwd16(const CtrlNodeBwdArgs& a, int num_blocks, hip
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)N16_LDS);
     hipLaunchKernelGGL(kern, dim3(num_blocks), dim3(N16_NW * 64), N16_LDS, st, a);
   };
-  if (a.stamps) go(ctrl_node_bwd16_kernel<D, true>);
+  if (a.a_max != 0.f) go(ctrl_node_bwd16_kernel<D | N16_LIM, false>);      // (no phase clocks under the limit)
+  else if (a.stamps) go(ctrl_node_bwd16_kernel<D, true>);
   else go(ctrl_node_bwd16_kernel<D, false>);
 }
 

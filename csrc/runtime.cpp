@@ -64,6 +64,8 @@ class RolloutDriver {
     if (!s.S || a.S != s.S || sort_.S != s.S || !s.idx || a.idx != s.idx || !s.dang || !s.cnt || !a.A || !a.Snext ||
         !a.dist_sum || !a.act_sum || !a.pooled || !a.argmax || !host_dist_)
       throw std::invalid_argument("RolloutDriver: a required buffer is missing");
+    if (!(a.a_max >= 0.f) || std::isinf(a.a_max))
+      throw std::invalid_argument("RolloutDriver: a_max is 0 (off) or a positive finite limit");
     if (small_ctl_) {
       chk(hipHostMalloc((void**)&small_res_, 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
       small_res_[0] = small_res_[1] = 0;
@@ -378,6 +380,8 @@ class BpttDriver {
     if (!n.S || !n.pooled || !n.A || !n.valid || !n.ego || !n.partial || !e.idx || !e.argmax || !e.dEc || !e.partial ||
         !dS_ || !Gb_ || !rptr_ || !redges_)
       throw std::invalid_argument("BpttDriver: a required buffer is missing");
+    if (!(n.a_max >= 0.f) || std::isinf(n.a_max))
+      throw std::invalid_argument("BpttDriver: a_max is 0 (off) or a positive finite limit");
   }
 
   // use_acts: this iteration's rollout kept the node activations (RolloutDriver with node_acts)

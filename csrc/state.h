@@ -50,4 +50,20 @@ DEV float sqsum(const float (&x)[D]) {
   return s;
 }
 
+// Actuator limit of the training rollout (semantics: macbf_gnn_amd/oracle.py, "Actuator limit").
+// The applied action: comparisons, so a NaN stays a NaN (torch.clamp).
+DEV float limit_action(float av, float a_max) { return av < -a_max ? -a_max : (av > a_max ? a_max : av); }
+
+// The clamp's adjoint on dL/du (torch.clamp's autograd rule): kept where -a_max <= a <= a_max,
+// the boundary included; exactly zero where the raw action a is outside the box or NaN.
+// a_max = 0 is "no limit" and leaves da as it is, behind one scalar test (the node-backward kernels
+// call this from their LIM instantiations only: csrc/ctrl.hip node_bwd_body, csrc/node16.h).
+template <int D>
+DEV void limit_adjoint(float (&da)[D], const float (&av)[D], float a_max) {
+  if (a_max != 0.f) {
+#pragma unroll
+    for (int q = 0; q < D; ++q) da[q] = (av[q] >= -a_max && av[q] <= a_max) ? da[q] : 0.f;
+  }
+}
+
 }  // namespace mb

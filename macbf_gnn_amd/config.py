@@ -98,6 +98,9 @@ class TrainConfig:
     obstacle_points: int = 12
     cbf_dedup: bool = True            # HIP, BPTT: evaluate h'(s_{t+1}) through the next step's h of the
                                       # same neighbour pair (~1.08 E instead of 2 E CBF evaluations)
+    a_max: float = 0.0                # per-axis actuator limit of the TRAINING rollouts: the Euler step applies
+                                      # clamp(a, -a_max, a_max), the backward masks dL/da (oracle.py, "Actuator
+                                      # limit"); 0: off -- nothing changes by a bit. val_a_max does not follow it
     # validation during training (macbf_gnn_amd/validate.py); everything is off with val_every = 0
     val_every: int = 0                # closed-loop validation every this many iterations (0: never)
     val_envs: int = 4                 # held-out scenes per rank, fixed for the whole run
@@ -106,7 +109,7 @@ class TrainConfig:
     val_impl: str = "python"          # "python": the rollout as torch ops | "native" (HIP only, opt-in): one
                                       # native call per rollout (ops/episode.py), the same integer totals
     val_a_max: float = 0.0            # per-axis actuator limit |u| <= val_a_max on both validation rollouts
-                                      # (evaluate.py, "Actuator limit"); 0: off. Training rollouts are not touched
+                                      # (evaluate.py, "Actuator limit"); 0: off. The training rollouts' limit is a_max
     save_best: bool = False           # keep <model_path>.best (+ .best.json) at the best validation so far
     best_metric: str = ""             # a val_*_rate key, higher is better; "": val_refined_safety_rate
                                       # (val_safety_rate with val_refine off)

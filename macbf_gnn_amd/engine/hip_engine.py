@@ -74,6 +74,11 @@ class HipEngine:
         self.native_bptt = bool(knobs.get_int("MACBF_NATIVE_BPTT", int(self.native_bptt)))
         self.bptt = cfg.bptt
         self.reuse = cfg.reuse_nbr_idx
+        # the training rollout's actuator limit (oracle.py, "Actuator limit"): the fp32 value every
+        # path compares with, or None -- then no launch gets the key and nothing changes
+        from ..evaluate import check_a_max
+        self.a_max = check_a_max(getattr(cfg, "a_max", 0.0) or None)
+        self._last_T = None            # horizon of the last step() (limited_counts)
         # deduplicated h/h' evaluations need both roles' state gradients on the same s_t: BPTT only
         self.dedup = bool(getattr(cfg, "cbf_dedup", True)) and cfg.bptt
         native.lib()
@@ -382,7 +387,7 @@ class HipEngine:
             ctrl, prec, ncu = native._ctrl_fwd_kw(self.S[0], self.G, self.idx[0], pw.ctrl_w, pw.ctrl_off["ew1f"],
                                                   pw.ctrl_off["nw1f"], pw.ctrl_v, self.A[0], self.S[1], self.dist[0],
                                                   self.act[0], **self._noise_args(), pooled=self.pooled[0],
-                                                  argmax=self.argmax[0], prec=self.prec)
+                                                  argmax=self.argmax[0], prec=self.prec, a_max=self.a_max)
             hfwd = native._cbf_hfwd_kw(self.S, self.idx[:T], self.idx[:T], self.src, self.nev_host, pw.cbf_w,
                                        pw.cbf_off["w1f"], pw.cbf_rm, pw.cbf_v, self.hbuf, self.hmask,
                                        prec=self.prec)[0] if overlap else None
@@ -450,7 +455,7 @@ class HipEngine:
                         prev_idx=self.idx[t - 1] if t > 0 else None, sort=t % self.resort_every == 0)
             native.ctrl_fwd(self.S[t], self.G, self.idx[t], pw.ctrl_w, pw.ctrl_off["ew1f"], pw.ctrl_off["nw1f"],
                             pw.ctrl_v, self.A[t], self.S[t + 1], self.dist[t], self.act[t], noise_t=t, **self._noise_args(),
-                            pooled=self.pooled[t], argmax=self.argmax[t], prec=self.prec)
+                            pooled=self.pooled[t], argmax=self.argmax[t], prec=self.prec, a_max=self.a_max)
             if early_stop:
                 # the per-env goal distances go to pinned host memory on a side stream (the
                 # blit stays off the compute queue's critical path)
@@ -510,11 +515,19 @@ class HipEngine:
     def trajectory(self, T: int) -> dict:
         """The last rollout of T steps in the oracle's layout (``oracle.rollout(forced=...)``):
         agent states (B, T+1, N, 2D), neighbour graphs (B, T, N, K) and the controller's
-        max-pool argmax slots (B, T, N, 128) -- tests replay it through the oracle."""
+        max-pool argmax slots (B, T, N, 128) -- tests replay it through the oracle. "A": the raw
+        actions (B, T, N, D) and, under an actuator limit, "sat" int8 (B, T, N, D): -1 / 0 / +1 where the
+        raw action is below -a_max / inside (the boundary included) / above a_max, and 2 where it is NaN
+        (applied as it is, no gradient) -- the kernels' decisions, from the same fp32 numbers."""
         N = self.N
         S = native.from_records(self.S[: T + 1, :, :N]).transpose(0, 1).contiguous()
-        return {"S": S, "idx": self.idx[:T].transpose(0, 1).long().contiguous(),
-                "slots": self.argmax[:T].transpose(0, 1).contiguous()}
+        A = self.A[:T].transpose(0, 1).contiguous()
+        out = {"S": S, "idx": self.idx[:T].transpose(0, 1).long().contiguous(),
+               "slots": self.argmax[:T].transpose(0, 1).contiguous(), "A": A}
+        if self.a_max is not None:
+            out["sat"] = ((A > self.a_max).to(torch.int8) - (A < -self.a_max).to(torch.int8)
+                          + 2 * torch.isnan(A).to(torch.int8))
+        return out
 
     # ------------------------------------------------------------------ step
     def step(self, s0, g, obs=None):
@@ -613,7 +626,8 @@ class HipEngine:
     def _graph_suffix(self):
         # (the flat gradient's address too: a checkpoint load that rebinds the flat buffers gets a
         # fresh graph; every other captured buffer lives as long as the engine)
-        return (self._gscale()[0], self.tr.fp.grad.data_ptr(), self.tr.fp.flat.data_ptr())
+        # (and the actuator limit, a captured kernel argument)
+        return (self._gscale()[0], self.tr.fp.grad.data_ptr(), self.tr.fp.flat.data_ptr(), self.a_max)
 
     # ------------------------------------------------------------------ graph mode
     def _step_graph(self, s0, g, obs):
@@ -801,7 +815,7 @@ class HipEngine:
                                  self.A[:T].view(TB, N, D), self.dS[1: T + 1].view(TB, N, W), valid_u8.view(TB),
                                  pw.ctrl_rm, pw.node_rm_off, pw.ctrl_v, gs * ACT_COEF, dP[:TB], None, pn, nb_n,
                                  act_cnt=self.counts[2:3], prec=self.prec, init=True, gscale=gsd,
-                                 wrm16=self._node16(TB * N))
+                                 wrm16=self._node16(TB * N), a_max=self.a_max)
             native.ctrl_edge_bwd(self.S[:T].view(TB, Nn, W), self.idx[:T].view(TB, N, K), self.argmax[:T].view(TB, N, 128),
                                  dP[:TB], pw.ctrl_w, pw.ctrl_off["ew1f"], pw.ctrl_off["ew2tn"], None, pe, nb_e, prec=self.prec,
                                  init=True)
@@ -892,7 +906,8 @@ class HipEngine:
             node, prec = native._node_bwd_kw(
                 self.pooled[0], self.S[0], self.G, self.A[0], self.dS[0], self.valid_buf[0], pw.ctrl_rm, pw.node_rm_off,
                 pw.ctrl_v, 0.0, self.dP, self.ego, self.part_node[: self.nb_node], self.nb_node, act_cnt=self.counts[2:3],
-                prec=self.prec, gscale=getattr(self.tr, "gscale_dev", None), wrm16=self._node16(B * N))
+                prec=self.prec, gscale=getattr(self.tr, "gscale_dev", None), wrm16=self._node16(B * N),
+                a_max=self.a_max)
             edge, _ = native._edge_bwd_kw(
                 self.S[0], self.idx[0], self.argmax[0], self.dP, pw.ctrl_w, pw.ctrl_off["ew1f"], pw.ctrl_off["ew2tn"],
                 self.dEc[0], self.part_edge[: self.nb_edge], self.nb_edge, prec=self.prec,
@@ -928,7 +943,7 @@ class HipEngine:
                         valid_t=valid_u8[t][sl], wrm=pw.ctrl_rm, offs=pw.node_rm_off, wvec=pw.ctrl_v,
                         act_coef=gs * ACT_COEF, dP=self.dP[sl], ego=self.ego[sl], partial=pn,
                         act_cnt=self.counts[2:3], prec=self.prec, init=init,
-                        gscale=getattr(self.tr, "gscale_dev", None), combine=cmb)
+                        gscale=getattr(self.tr, "gscale_dev", None), combine=cmb, a_max=self.a_max)
             edge = dict(S=self.S[t][sl], idx=self.idx[t][sl], argmax=self.argmax[t][sl], dP=self.dP[sl], wpack=pw.ctrl_w,
                         f_ew1f=pw.ctrl_off["ew1f"], f_ew2tn=pw.ctrl_off["ew2tn"], dEc=self.dEc[t & 1][sl], partial=pe,
                         prec=self.prec, init=init)
@@ -951,8 +966,20 @@ class HipEngine:
         if work is not None:
             work.wait()
 
+    def limited_counts(self):
+        """(valid agent-steps of the last step() with some |a_q| > a_max, valid agent-steps) as device
+        tensors, or None without a limit or a step: torch ops on the stored raw actions and the
+        validity mask, outside the step itself (Trainer.limited_rate, logging iterations)."""
+        if self.a_max is None or self._last_T is None:
+            return None
+        T = self._last_T
+        valid = self.valid_buf[:T] != 0                         # (T, B)
+        lim = ((self.A[:T].abs() > self.a_max).any(-1) & valid[..., None]).sum()
+        return lim, valid.sum() * self.N
+
     def _stats(self, raw, T):
         from ..utils.metrics import StepStats
+        self._last_T = self.Tmax if isinstance(T, torch.Tensor) else int(T)    # (graph mode: Tmax, masked)
         if self.graph_mode:      # the captured graph writes fixed buffers
             return StepStats(raw.clone(), T.clone() if isinstance(T, torch.Tensor) else T)
         return StepStats(raw, T)

@@ -17,6 +17,9 @@ class OracleEngine:
 
     def __init__(self, trainer):
         self.tr = trainer
+        from ..evaluate import check_a_max
+        self.a_max = check_a_max(getattr(trainer.cfg, "a_max", 0.0) or None)    # the fp32 limit, or None
+        self._last = None
 
     def after_update(self, commit=None):
         if commit is not None:          # a trainer on a HIP device: the deferred optimizer commit
@@ -33,7 +36,9 @@ class OracleEngine:
                               bptt=cfg.bptt, early_stop=cfg.early_stop,
                               noise_prob=cfg.add_noise_prob, noise_scale=cfg.noise_scale,
                               generator=tr.torch_gen, compute_safety=cfg.compute_safety, obs=obs,
-                              forced=forced)
+                              forced=forced, a_max=self.a_max)
+        # the last rollout (detached): raw actions (B, T, N, D), validity (B, T), states (B, T+1, N, 2D)
+        self._last = (traj["A"].detach(), traj["valid"], traj["S"].detach())
         tr.timer.mark("rollout")
         T = traj["A"].shape[1]
         valid = traj["valid"]
@@ -67,3 +72,12 @@ class OracleEngine:
             "agent_steps": agent_steps, "safe_agents": safe, "T": T,
         }
         return stats
+
+    def limited_counts(self):
+        """(valid agent-steps of the last rollout with some |a_q| > a_max, valid agent-steps), or None
+        without a limit or a rollout."""
+        if self.a_max is None or self._last is None:
+            return None
+        A, valid, _ = self._last
+        lim = ((A.abs() > self.a_max).any(-1) & valid[..., None]).sum()
+        return lim, valid.sum() * A.shape[2]

@@ -61,6 +61,12 @@ class Trainer:
         torch.manual_seed(cfg.seed)
         if cfg.dim not in (2, 3):
             raise ValueError("dim must be 2 or 3")
+        if cfg.a_max != 0.0:              # 0: off; anything else is a positive finite fp32 limit
+            from ..evaluate import check_a_max
+            try:
+                check_a_max(cfg.a_max)
+            except ValueError as e:
+                raise ValueError(f"a_max must be a positive finite number, or 0 for no limit: {e}") from None
         self.controller = Controller(2 * cfg.dim).to(self.device)
         self.cbf = CBF(2 * cfg.dim).to(self.device)
         self.fp = FlatParams({"controller": self.controller, "cbf": self.cbf}, device=self.device)
@@ -258,7 +264,8 @@ class Trainer:
             stats = self.train_step()
             self.logger.update(stats)
             if (self.step_count % max(self.cfg.display_steps, 1)) == 0:
-                last = self.logger.emit(self.step_count)
+                lr_ = self.limited_rate()      # (a collective under DP: every rank logs at the same steps)
+                last = self.logger.emit(self.step_count, {} if lr_ is None else {"limited_rate": lr_})
             if self.cfg.model_path and (self.step_count % max(self.cfg.save_steps, 1)) == 0:
                 ckpt.save(self, self.cfg.model_path)
                 self.dp.barrier()
@@ -268,6 +275,19 @@ class Trainer:
             ckpt.save(self, self.cfg.model_path)      # final state of the run
             self.dp.barrier()
         return last
+
+    def limited_rate(self):
+        """Under ``cfg.a_max``: the share of the last rollout's valid agent-steps (all ranks) whose raw
+        action has some component with |a_q| > a_max; None without a limit. Torch ops on the stored
+        actions and the validity mask, and one host read: for logging iterations, not for every step."""
+        lc = getattr(self.engine, "limited_counts", None)
+        c = lc() if lc is not None else None
+        if c is None:
+            return None
+        v = torch.stack([c[0].to(torch.float64), c[1].to(torch.float64)])
+        self.dp.all_reduce_(v)
+        lim, tot = v.tolist()
+        return lim / tot if tot > 0 else 0.0
 
     # ------------------------------------------------------------------ validation
     def validate(self):

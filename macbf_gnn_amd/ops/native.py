@@ -372,8 +372,10 @@ def _records(t, name, lead, W, min_rows=None):
 
 
 def _ctrl_fwd_kw(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise=None, pooled=None, argmax=None,
-                 prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None):
-    """ctrl_fwd's checks -> (the CtrlArgs fields (csrc/args.h) as a dict, precision code, num_cu)."""
+                 prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None, a_max=None):
+    """ctrl_fwd's checks -> (the CtrlArgs fields (csrc/args.h) as a dict, precision code, num_cu).
+    a_max (optional): the training rollout's per-axis actuator limit (oracle.py, "Actuator limit"); the
+    key is only there with a limit, so a call without one passes what it always passed."""
     B, N, K = idx.shape
     D = dim_of(S)
     W = rec_width(D)
@@ -422,17 +424,20 @@ def _ctrl_fwd_kw(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_su
               dim=D, apw=ctrl_fwd_apw(B * N, S.device, N),
               noise_key=ptr(noise_key), noise_prob=float(noise_prob), noise_scale=float(noise_scale),
               noise_t=int(noise_t), stamps=ptr(stamps))
+    if _a_max(a_max) > 0.0:
+        kw["a_max"] = _a_max(a_max)
     return kw, f16, num_cu(S.device)
 
 
 def ctrl_fwd(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise=None, pooled=None, argmax=None,
-             prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None):
+             prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None, a_max=None):
     """Fused controller step on per-step views: S/Sn (B,Nn,W) node records (agents first),
     G (B,N,D), idx (B,N,K), A (B,N,D), dist_sum/act_sum (B,) int64 fixed point (x FX_DIST /
     x FX_ACT: order-independent integer atomics), pooled (B,N,128) bf16
-    ((B,N,256) [hi | lo] rows for prec="fp32", required there), argmax (B,N,128) uint8."""
+    ((B,N,256) [hi | lo] rows for prec="fp32", required there), argmax (B,N,128) uint8.
+    a_max (optional): Sn applies clamp(a, -a_max, a_max); A and act_sum keep the raw action."""
     kw, f16, ncu = _ctrl_fwd_kw(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise, pooled, argmax,
-                                prec, noise_key, noise_prob, noise_scale, noise_t, stamps)
+                                prec, noise_key, noise_prob, noise_scale, noise_t, stamps, a_max)
     _ok(lib().ctrl_fwd(num_cu=ncu, prec=f16, stream=stream_handle(), **kw), "ctrl_fwd")
 
 
@@ -1102,8 +1107,10 @@ NODE16_RM = 64 * 176 + 128 * 80 + 64 * 144 + 16 * 80    # csrc/node16.h: element
 
 
 def _node_bwd_kw(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
-                 act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, wrm16=None):
-    """ctrl_node_bwd's checks -> (the CtrlNodeBwdArgs fields (csrc/args.h) as a dict, precision code)."""
+                 act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, wrm16=None,
+                 a_max=None):
+    """ctrl_node_bwd's checks -> (the CtrlNodeBwdArgs fields (csrc/args.h) as a dict, precision code).
+    a_max (optional): the rollout's actuator limit -- the key is only there with a limit."""
     B, N = G.shape[:2]
     D = dim_of(S)
     W = rec_width(D)
@@ -1156,18 +1163,23 @@ def _node_bwd_kw(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, eg
             raise NativeError("16x16x32 node backward: 128-agent chunks only")
         check(wrm16, wrm.dtype, (_planes(f16) * NODE16_RM,), "wrm16")
         kw["wrm16"] = ptr(wrm16)
+    if _a_max(a_max) > 0.0:
+        kw["a_max"] = _a_max(a_max)
     return kw, f16
 
 
 def ctrl_node_bwd(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
-                  act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, wrm16=None):
+                  act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, wrm16=None,
+                  a_max=None):
     """act_cnt: optional 1-element device tensor holding the (all-reduced) action-loss count
     n_act; the action-loss coefficient is then act_coef / max(n_act, 1), read by the kernel (no
     host round trip, no extra launch). init: write the weight-gradient slabs instead of
     accumulating into them (no zero fill needed). stamps: diagnostics only, int64
-    (num_blocks, 4, 16) phase clocks of the cooperative 32-agent path (scripts/stamps_node.py)."""
+    (num_blocks, 4, 16) phase clocks of the cooperative 32-agent path (scripts/stamps_node.py).
+    a_max (optional): the rollout's actuator limit -- dL/da through the Euler step is zero where the
+    raw action A lies outside [-a_max, a_max] or is NaN (the action-loss term is kept)."""
     kw, f16 = _node_bwd_kw(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
-                           act_cnt, prec, init, chunk, gscale, combine, stamps, wrm16)
+                           act_cnt, prec, init, chunk, gscale, combine, stamps, wrm16, a_max)
     _ok(lib().ctrl_node_bwd(num_blocks=int(num_blocks), prec=f16, stream=stream_handle(), **kw), "ctrl_node_bwd")
 
 

@@ -17,6 +17,33 @@ for the D-dimensional double integrator (D = 2: the reference; D = 3: BASELINE c
 Functions accept any leading batch dims ``...`` in front of (N, ·). Static obstacles
  enter as extra non-controlled graph nodes: ``nodes = cat(s, [o, 0])``; agents
 are the first N nodes, so agent i is node i and self stays at kNN slot 0.
+
+Actuator limit (``rollout(a_max=)``, ``TrainConfig.a_max``, ``train.py --a_max``; opt-in). The one
+statement of what training under a per-axis actuator limit means; the kernels (``csrc/ctrl.hip``
+``node_phase``, ``csrc/state.h`` ``limit_action`` / ``limit_adjoint``) and ``docs/ARCHITECTURE.md``
+point here. ``a_max`` is None (off) or a positive finite fp32 value (``evaluate.check_a_max``); in the
+native argument structs 0 means off. Per rollout step and action component q::
+
+    a_q  = PD law (+ exploration noise)       raw action: what A stores, what the action loss sees
+    u_q  = a_q < -a_max ? -a_max : a_q > a_max ? a_max : a_q      applied action (comparisons: a NaN
+                                              stays a NaN, as torch.clamp)
+    v'_q = v_q + u_q * dt                     (multiply, then add; no contraction)
+    du_q / da_q = 1 if -a_max <= a_q <= a_max else 0              (torch.clamp's autograd rule: the
+                                              boundary passes, a NaN gives 0)
+
+* ``A`` keeps the raw action. The backward kernels reload it for the action-loss gradient and
+  recompute the mask from that same fp32 number; a stored clamped value could not tell a boundary
+  value from a saturated one.
+* The action regulariser stays on the raw action (``action_loss_terms``, the forward's action sum,
+  the backward's ``da += c * 2 * a``): it is the only gradient a saturated component still gets and
+  pulls it back towards the box. The loss value is what it is without a limit.
+* Exploration noise is added before the clamp: the actuator clips whatever is commanded.
+* Obstacle nodes have no action; nothing changes for them.
+* The CBF losses need no change: they read S[t] and S[t+1], and their gradient reaches a_t only
+  through dL/dS[t+1], which the mask multiplies -- with or without BPTT, with either neighbour set
+  for h'.
+* With the limit off nothing changes by a bit.
+
 Reference cites: kNN ``core.py:234-250``; controller ``controller.py:31-63``; CBF
 ``cbf.py:21-45``; TTC ``core.py:187-231``; losses ``core.py:89-184``; loop ``train.py:48-105``.
 """
@@ -362,7 +389,7 @@ def finalize_losses(sums, n_act_sum, n_act):
 # ----------------------------------------------------------------------------- rollout
 def rollout(ctrl_params, s0, g, *, top_k=C.TOP_K, inner_loops=C.INNER_LOOPS, bptt=True,
             early_stop=True, noise_prob=0.0, noise_scale=C.NOISE_SCALE, generator=None,
-            compute_safety=False, obs=None, forced=None):
+            compute_safety=False, obs=None, forced=None, a_max=None):
     """Batched rollout with per-env done masks (train.py:58-81).
 
     Returns dict with S (B,T+1,N,4), A (B,T,N,2), idx (B,T,N,K), valid (B,T) bool,
@@ -373,7 +400,16 @@ def rollout(ctrl_params, s0, g, *, top_k=C.TOP_K, inner_loops=C.INNER_LOOPS, bpt
     while their gradients follow this rollout's own expressions (straight-through:
     s_{t+1} = S_{t+1} + (e - e.detach()), e = s_t + dt [v, a]), so the gradient is the oracle's
     gradient along exactly that trajectory, graph and pooling choice.
+
+    ``a_max``: the actuator limit of the module docstring -- the Euler step applies
+    clamp(a, -a_max, a_max); ``A`` in the returned dict stays the raw action. With ``forced["sat"]``
+    (int8 (B,T,N,D) of -1 / 0 / +1, e.g. ``HipEngine.trajectory()``; 2 marks a NaN action, applied as
+    it is with no gradient, as clamp does) the applied action is where(sat == 0, a, sat * a_max): the gradient mask is the replayed engine's decision, not this
+    rollout's own comparison, so a near-tie at the limit cannot flip a discrete choice between the two.
     """
+    if a_max is not None:
+        from .evaluate import check_a_max
+        a_max = check_a_max(a_max)
     B = s0.shape[0]
     s = s0
     active = torch.ones(B, dtype=torch.bool, device=s0.device)
@@ -395,7 +431,15 @@ def rollout(ctrl_params, s0, g, *, top_k=C.TOP_K, inner_loops=C.INNER_LOOPS, bpt
             coin = torch.rand(B, generator=generator, device=s.device) < noise_prob
             nz = torch.randn(a.shape, generator=generator, device=s.device) * noise_scale
             a = a + nz * coin[:, None, None].to(a.dtype)
-        s_next = s + torch.cat([s[..., dim:], a], -1) * C.TIME_STEP
+        u = a
+        if a_max is not None:
+            sat = None if forced is None else forced.get("sat")
+            if sat is None:
+                u = torch.clamp(a, -a_max, a_max)
+            else:
+                st = sat[:, t].to(a.device)
+                u = torch.where(st == 0, a, torch.where(st == 2, a.detach(), st.to(a.dtype) * a_max))
+        s_next = s + torch.cat([s[..., dim:], u], -1) * C.TIME_STEP
         if forced is not None:
             s_next = forced["S"][:, t + 1] + (s_next - s_next.detach())
         dist = torch.linalg.norm(s_next[..., :dim] - g, dim=-1).mean(-1)

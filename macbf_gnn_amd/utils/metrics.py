@@ -148,8 +148,10 @@ class MetricsLogger:
         out["agent_steps_per_s"] = d["agent_steps"] / max(dt, 1e-9)
         return out
 
-    def emit(self, step):
+    def emit(self, step, extra=None):
+        """``extra``: further entries of this line (already reduced over the ranks)."""
         out = self.summary(step)
+        out.update(extra or {})
         if self.dp.rank == 0:
             line = json.dumps(out)
             print(line, file=self.stream, flush=True)
