@@ -315,9 +315,6 @@ struct CtrlNodeBwdArgs {
   float a_max;
 };
 
-// the cooperative 32-agent node backward (node_bwd_coop) runs every 32-agent chunk
-inline bool node_bwd_coop_enabled() { return true; }
-
 struct CtrlEdgeBwdArgs {
   const float4* S;     long s_env;     // node records (strides in records)
   int dim;

@@ -16,6 +16,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 #include "state.h"
 #include "cbf_edge.h"   // cbf_edge_frag, EdgeCtx, weight-image sizes (shared with refine.hip)
 
@@ -198,14 +199,9 @@ extern "C" int MB_SYM(cbf_fwd)(const mb::CbfFwdArgs* a, int num_blocks, hipStrea
   using namespace mb::MB_PREC;
   if (a->K > 16 || a->K < 1) return -1;
   const size_t lds = (size_t)CBF_FWD_FRAGS * FRAG_SZ + CBF_VEC * 4;
-  if (a->dim == 3) {
-    (void)hipFuncSetAttribute((const void*)cbf_fwd_kernel<CBF_FWD_WAVES, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((cbf_fwd_kernel<CBF_FWD_WAVES, 3>), dim3(num_blocks), dim3(CBF_FWD_WAVES * 64), lds, st, *a);
-  } else {
-    (void)hipFuncSetAttribute((const void*)cbf_fwd_kernel<CBF_FWD_WAVES, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((cbf_fwd_kernel<CBF_FWD_WAVES, 2>), dim3(num_blocks), dim3(CBF_FWD_WAVES * 64), lds, st, *a);
-  }
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) {
+    return launch_lds(cbf_fwd_kernel<CBF_FWD_WAVES, D()>, dim3(num_blocks), dim3(CBF_FWD_WAVES * 64), lds, st, *a);
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -848,13 +844,6 @@ __global__ __launch_bounds__(NW * 64, 1) void cbf_bwd_kernel(CbfBwdArgs a) {
   }
 }
 
-template <bool FUSED, int NW, int D>
-static void launch_cbf_bwd(const CbfBwdArgs& a, int num_blocks, hipStream_t st) {
-  const size_t lds = CbfCfg<NW>::LDS;
-  (void)hipFuncSetAttribute((const void*)cbf_bwd_kernel<FUSED, NW, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((cbf_bwd_kernel<FUSED, NW, D>), dim3(num_blocks), dim3(NW * 64), lds, st, a);
-}
-
 }  // namespace MB_PREC
 }  // namespace mb
 
@@ -868,21 +857,16 @@ extern "C" int MB_SYM(cbf_bwd)(const mb::CbfBwdArgs* a, int num_blocks, hipStrea
   if (a->K > 16 || a->K < 1 || a->passes < 1 || a->passes > 2) return -1;
   if (a->rec) {   // 16x16x32 backward over cbf_compact's records (csrc/cbf16.h)
     if (a->fused || !a->nact || !a->wrm16 || !a->w16) return -5;
-    if (a->dim == 3) launch_cbf_bwd16<3>(*a, num_blocks, st);
-    else launch_cbf_bwd16<2>(*a, num_blocks, st);
-    return (int)hipGetLastError();
+    return by_dim(a->dim, [&](auto D) { return launch_cbf_bwd16<D()>(*a, num_blocks, st); });
   }
   if (a->fused && (a->passes != 2 || !a->dang || !a->counts)) return -2;
   if (a->src && (a->fused || !a->nev || a->passes != 2)) return -3;
   if (a->act && (!a->src || !a->nact)) return -4;
-  if (a->dim == 3) {
-    if (a->fused) launch_cbf_bwd<true, CBF_NW, 3>(*a, num_blocks, st);
-    else launch_cbf_bwd<false, CBF_NW, 3>(*a, num_blocks, st);
-  } else {
-    if (a->fused) launch_cbf_bwd<true, CBF_NW, 2>(*a, num_blocks, st);
-    else launch_cbf_bwd<false, CBF_NW, 2>(*a, num_blocks, st);
-  }
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) {
+    return by_flag(a->fused != 0, [&](auto FUSED) {
+      return launch_lds(cbf_bwd_kernel<FUSED(), CBF_NW, D()>, dim3(num_blocks), dim3(CBF_NW * 64), CbfCfg<CBF_NW>::LDS, st, *a);
+    });
+  });
 }
 
 extern "C" int MB_SYM(cbf_hfwd)(const mb::CbfFwdArgs* a, int num_blocks, hipStream_t st) {
@@ -890,12 +874,7 @@ extern "C" int MB_SYM(cbf_hfwd)(const mb::CbfFwdArgs* a, int num_blocks, hipStre
   using namespace mb::MB_PREC;
   if (a->K > 16 || a->K < 1) return -1;
   if (!a->src || !a->nev || !a->idx1 || !a->h_out || !a->mask_out || !a->wrm) return -2;
-  if (a->dim == 3) {
-    (void)hipFuncSetAttribute((const void*)cbf_hfwd_kernel<HFWD_WAVES, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HFWD_LDS);
-    hipLaunchKernelGGL((cbf_hfwd_kernel<HFWD_WAVES, 3>), dim3(num_blocks), dim3(HFWD_WAVES * 64), HFWD_LDS, st, *a);
-  } else {
-    (void)hipFuncSetAttribute((const void*)cbf_hfwd_kernel<HFWD_WAVES, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HFWD_LDS);
-    hipLaunchKernelGGL((cbf_hfwd_kernel<HFWD_WAVES, 2>), dim3(num_blocks), dim3(HFWD_WAVES * 64), HFWD_LDS, st, *a);
-  }
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) {
+    return launch_lds(cbf_hfwd_kernel<HFWD_WAVES, D()>, dim3(num_blocks), dim3(HFWD_WAVES * 64), HFWD_LDS, st, *a);
+  });
 }

@@ -438,13 +438,10 @@ __global__ __launch_bounds__(C16_NW * 64, 2 * C16_WG_PER_CU) void cbf_bwd16_kern
 }
 
 template <int D>
-static void launch_cbf_bwd16(const CbfBwdArgs& a, int num_blocks, hipStream_t st) {
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C16_LDS);
-    hipLaunchKernelGGL(kern, dim3(num_blocks), dim3(C16_NW * 64), C16_LDS, st, a);
-  };
-  if (a.stamps) go(cbf_bwd16_kernel<D, true>);
-  else go(cbf_bwd16_kernel<D, false>);
+static int launch_cbf_bwd16(const CbfBwdArgs& a, int num_blocks, hipStream_t st) {
+  return by_flag(a.stamps != nullptr, [&](auto ST) {
+    return launch_lds(cbf_bwd16_kernel<D, ST()>, dim3(num_blocks), dim3(C16_NW * 64), C16_LDS, st, a);
+  });
 }
 
 }  // namespace MB_PREC

@@ -17,6 +17,7 @@
 #include <climits>
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 #include "state.h"
 #include "ttc.h"
 #include "combine.h"
@@ -517,13 +518,13 @@ DEV void pool_dense12(const CtrlArgs& a, const AgentBase& ab, int g0, int APW, i
 
 // Controller step. bf16 / fp16: edge and node phase in one kernel, the pooled features cross
 // from the edge lanes (features) to the node lanes (agents) through a per-wave LDS image.
-// x3: the split weights do not fit one workgroup's LDS together, so this kernel runs the edge
-// phase only and writes the pooled features ([hi | lo] rows, always stored) straight to global
-// memory; ctrl_node_fwd_kernel reads them back as node-layer B fragments.
+// x3: the edge phase writes the pooled features ([hi | lo] rows, always stored) straight to global
+// memory, and the same wave reads them back as node-layer B fragments for the group's node phase
+// (GNODE, the fused step).
 // Body of the controller step over the agent groups grp0, grp0 + gstride, ... of `a` (weights
 // already in LDS: wl = ew1f|ew2, wn = nw1f..nw4, vl = CTRL_VEC floats, pools = one 32-row pool
-// image per wave). SPLIT (always for x3): edge phase only, the pooled rows go to global memory
-// and ctrl_node_groups runs the node phase.
+// image per wave). SPLIT (the persistent small-scene rollout): edge phase only, the pooled rows go
+// to global memory and ctrl_node_groups runs the node phase.
 constexpr int CTRL_HOIST_EB = 1;
 constexpr int CTRL_FWD_DENSE = 1;
 // DENSE12 (K = 12, agents per wave a multiple of 8): dense edge rows -- a group's APW agents x 12
@@ -758,14 +759,14 @@ DEV void publish_step(const CtrlArgs& a) {
 template <int WAVES, int D, bool FUSE, bool ST, bool ACTS, bool LIM = false>
 DEV void ctrl_fwd_body(const CtrlArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  static_assert(FUSE == X3, "the x3 step is the fused one; FUSE stays a parameter for the kernel names");
   const unsigned long long t0 = ST ? __builtin_amdgcn_s_memtime() : 0ull;
-  constexpr int NFR = (X3 && !FUSE) ? 18 : CTRL_FWD_FRAGS;          // fragments staged in LDS
   h16* wl = reinterpret_cast<h16*>(smem);                            // ew1f, ew2 (18 frags)
   h16* wn = wl + 18 * FRAG_ELEMS;                                     // nw1f..nw4 (54 frags)
-  float* vl = reinterpret_cast<float*>(smem + NFR * FRAG_SZ);
-  h16* pools = reinterpret_cast<h16*>(smem + NFR * FRAG_SZ + CTRL_VEC * 4);
+  float* vl = reinterpret_cast<float*>(smem + CTRL_FWD_FRAGS * FRAG_SZ);
+  h16* pools = reinterpret_cast<h16*>(smem + CTRL_FWD_FRAGS * FRAG_SZ + CTRL_VEC * 4);
   block_copy16(wl, a.wpack + (size_t)a.f_edge * FRAG_ELEMS, 18 * FRAG_SZ, false);
-  if constexpr (!X3 || FUSE) block_copy16(wn, a.wpack + (size_t)a.f_node * FRAG_ELEMS, 54 * FRAG_SZ, false);
+  block_copy16(wn, a.wpack + (size_t)a.f_node * FRAG_ELEMS, 54 * FRAG_SZ, false);
   block_copy16(vl, a.wvec, CTRL_VEC * 4);
   __syncthreads();
   const int apw = (a.apw >= 2 && a.apw <= 32) ? a.apw : 32;
@@ -778,7 +779,7 @@ DEV void ctrl_fwd_body(const CtrlArgs& a) {
     ctrl_fwd_groups<D, false, FUSE, true, ST, ACTS, LIM>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
   else
     ctrl_fwd_groups<D, false, FUSE, false, ST, ACTS, LIM>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
-  if constexpr (!X3 || FUSE) publish_step(a);   // the x3 split path publishes from its node kernel
+  publish_step(a);
 }
 
 template <int WAVES, int D, bool FUSE = false, bool ST = false>
@@ -800,7 +801,7 @@ __global__ __launch_bounds__(WAVES * 64) void ctrl_fwd_lim_kernel(CtrlArgs a) {
 }
 
 // Node phase of the controller step over the pooled rows in global memory, 32-agent groups
-// grp0, grp0 + gstride, ... (x3 steps, and the persistent small-scene rollout)
+// grp0, grp0 + gstride, ... (the persistent small-scene rollout)
 template <int D, bool ACTS = false, bool LIM = false>
 DEV void ctrl_node_groups(const CtrlArgs& a, const h16* wn, const float* vl, int grp0, int gstride) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -816,23 +817,12 @@ DEV void ctrl_node_groups(const CtrlArgs& a, const h16* wn, const float* vl, int
   }
 }
 
-// x3 node phase of the controller step over the pooled rows written by ctrl_fwd_kernel
-template <int WAVES, int D, bool ACTS = false>
-__global__ __launch_bounds__(WAVES * 64) void ctrl_node_fwd_kernel(CtrlArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  h16* wn = reinterpret_cast<h16*>(smem);                             // nw1f..nw4 (54 frags)
-  float* vl = reinterpret_cast<float*>(smem + 54 * FRAG_SZ);
-  block_copy16(wn, a.wpack + (size_t)a.f_node * FRAG_ELEMS, 54 * FRAG_SZ, false);
-  block_copy16(vl, a.wvec, CTRL_VEC * 4);
-  __syncthreads();
-  ctrl_node_groups<D, ACTS>(a, wn, vl, blockIdx.x * WAVES + wave_id(), gridDim.x * WAVES);
-  publish_step(a);
-}
-
 constexpr int CTRL_WAVES = 8;
 
+// x3 (the fused step): all 72 split fragments, 145 KB, one workgroup per CU; the pooled rows cross
+// through global memory, so no pool images
 size_t ctrl_fwd_lds() {
-  if constexpr (X3) return (size_t)18 * FRAG_SZ + CTRL_VEC * 4;
+  if constexpr (X3) return (size_t)CTRL_FWD_FRAGS * FRAG_SZ + CTRL_VEC * 4;
   return (size_t)CTRL_FWD_FRAGS * FRAG_BYTES + CTRL_VEC * 4 + (size_t)CTRL_WAVES * 32 * PSTR * 2;
 }
 
@@ -851,67 +841,17 @@ extern "C" int MB_SYM(ctrl_fwd)(const mb::CtrlArgs* a, int num_cu, hipStream_t s
   if (blocks > maxb) blocks = maxb;
   CtrlArgs b = *a;
   b.apw = apw;
-  // x3: one fused launch (edge + node phase per group, 145 KB of weights: one workgroup per CU)
-  if (X3) {
-    const size_t ldf = (size_t)CTRL_FWD_FRAGS * FRAG_SZ + CTRL_VEC * 4;
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldf);
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(CTRL_WAVES * 64), ldf, st, b);
-    };
-    // (4-wave workgroups for the slices' small grids -- one wave per SIMD on twice the CUs --
-    // measured no faster: 8-env slice 2.825-2.833 vs 2.797-2.820 ms, profiles/r6b/)
-    if (a->a_max != 0.f) {
-      if (a->dim == 3) {
-        if (a->acts) go(ctrl_fwd_lim_kernel<CTRL_WAVES, 3, true, true>);
-        else go(ctrl_fwd_lim_kernel<CTRL_WAVES, 3, true, false>);
-      } else {
-        if (a->acts) go(ctrl_fwd_lim_kernel<CTRL_WAVES, 2, true, true>);
-        else go(ctrl_fwd_lim_kernel<CTRL_WAVES, 2, true, false>);
-      }
-    } else if (a->dim == 3) {
-      if (a->stamps) go(ctrl_fwd_kernel<CTRL_WAVES, 3, true, true>);
-      else if (a->acts) go(ctrl_fwd_acts_kernel<CTRL_WAVES, 3, true>);
-      else go(ctrl_fwd_kernel<CTRL_WAVES, 3, true>);
-    } else {
-      if (a->stamps) go(ctrl_fwd_kernel<CTRL_WAVES, 2, true, true>);
-      else if (a->acts) go(ctrl_fwd_acts_kernel<CTRL_WAVES, 2, true>);
-      else go(ctrl_fwd_kernel<CTRL_WAVES, 2, true>);
-    }
-    return (int)hipGetLastError();
-  }
-  const size_t lds = ctrl_fwd_lds();
-  auto go1 = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(CTRL_WAVES * 64), lds, st, b);
-  };
-  if (!X3 && a->a_max != 0.f) {
-    if (a->dim == 3) {
-      if (a->acts) go1(ctrl_fwd_lim_kernel<CTRL_WAVES, 3, false, true>);
-      else go1(ctrl_fwd_lim_kernel<CTRL_WAVES, 3, false, false>);
-    } else {
-      if (a->acts) go1(ctrl_fwd_lim_kernel<CTRL_WAVES, 2, false, true>);
-      else go1(ctrl_fwd_lim_kernel<CTRL_WAVES, 2, false, false>);
-    }
-  } else if (a->dim == 3) {
-    if (a->acts) go1(ctrl_fwd_acts_kernel<CTRL_WAVES, 3>);
-    else go1(ctrl_fwd_kernel<CTRL_WAVES, 3>);
-  } else {
-    if (a->acts) go1(ctrl_fwd_acts_kernel<CTRL_WAVES, 2>);
-    else go1(ctrl_fwd_kernel<CTRL_WAVES, 2>);
-  }
-  if constexpr (X3) {
-    const size_t ldn = (size_t)54 * FRAG_SZ + CTRL_VEC * 4;
-    int nblocks = (a->B * a->N + 32 * CTRL_WAVES - 1) / (32 * CTRL_WAVES);     // 32-agent node groups
-    if (nblocks > maxb) nblocks = maxb;
-    if (a->dim == 3) {
-      (void)hipFuncSetAttribute((const void*)ctrl_node_fwd_kernel<CTRL_WAVES, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldn);
-      hipLaunchKernelGGL((ctrl_node_fwd_kernel<CTRL_WAVES, 3>), dim3(nblocks), dim3(CTRL_WAVES * 64), ldn, st, b);
-    } else {
-      (void)hipFuncSetAttribute((const void*)ctrl_node_fwd_kernel<CTRL_WAVES, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldn);
-      hipLaunchKernelGGL((ctrl_node_fwd_kernel<CTRL_WAVES, 2>), dim3(nblocks), dim3(CTRL_WAVES * 64), ldn, st, b);
-    }
-  }
-  return (int)hipGetLastError();
+  // (x3: 4-wave workgroups for the slices' small grids -- one wave per SIMD on twice the CUs --
+  // measured no faster: 8-env slice 2.825-2.833 vs 2.797-2.820 ms, profiles/r6b/)
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(blocks), dim3(CTRL_WAVES * 64), ctrl_fwd_lds(), st, b); };
+  return by_dim(a->dim, [&](auto D) {
+    if (a->a_max != 0.f)
+      return by_flag(a->acts != nullptr, [&](auto ACTS) { return go(ctrl_fwd_lim_kernel<CTRL_WAVES, D(), X3, ACTS()>); });
+    if constexpr (X3)       // phase clocks: the x3 step only
+      if (a->stamps) return go(ctrl_fwd_kernel<CTRL_WAVES, D(), X3, true>);
+    if (a->acts) return go(ctrl_fwd_acts_kernel<CTRL_WAVES, D(), X3>);
+    return go(ctrl_fwd_kernel<CTRL_WAVES, D(), X3>);
+  });
 }
 
 // =======================================================================================
@@ -2477,27 +2417,17 @@ extern "C" int MB_SYM(k16_wg_per_cu)(int kernel) {
 extern "C" int MB_SYM(ctrl_node_bwd)(const mb::CtrlNodeBwdArgs* a, int num_blocks, hipStream_t st) {
   using namespace mb;
   using namespace mb::MB_PREC;
-  if (a->wrm16) {   // 16x16x32 kernel (csrc/node16.h; 128-agent chunks)
-    if (a->dim == 3) launch_ctrl_node_bwd16<3>(*a, num_blocks, st);
-    else launch_ctrl_node_bwd16<2>(*a, num_blocks, st);
-    return (int)hipGetLastError();
-  }
-  const size_t lds = ctrl_node_bwd_lds();
+  if (a->wrm16)   // 16x16x32 kernel (csrc/node16.h; 128-agent chunks)
+    return by_dim(a->dim, [&](auto D) { return launch_ctrl_node_bwd16<D()>(*a, num_blocks, st); });
   CtrlNodeBwdArgs b = *a;
-  b.coop = node_bwd_coop_enabled() && a->chunk == 32;     // 32-agent chunks: the four waves cooperate
-  const void* fn = a->dim == 3 ? (b.coop ? (const void*)ctrl_node_bwd_coop_kernel<3> : (const void*)ctrl_node_bwd_kernel<3>)
-                               : (b.coop ? (const void*)ctrl_node_bwd_coop_kernel<2> : (const void*)ctrl_node_bwd_kernel<2>);
-  if (a->a_max != 0.f)      // the actuator limit: its own instantiations
-    fn = a->dim == 3 ? (b.coop ? (const void*)ctrl_node_bwd_coop_lim_kernel<3> : (const void*)ctrl_node_bwd_lim_kernel<3>)
-                     : (b.coop ? (const void*)ctrl_node_bwd_coop_lim_kernel<2> : (const void*)ctrl_node_bwd_lim_kernel<2>);
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  void* kargs[] = {&b};
-  const hipError_t rc = hipLaunchKernel(fn, dim3(num_blocks), dim3(NB_WAVES * 64), kargs, lds, st);
-  if (rc != hipSuccess) return (int)rc;
-  return (int)hipGetLastError();
+  b.coop = a->chunk == 32;     // 32-agent chunks: the four waves cooperate (node_bwd_coop)
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(num_blocks), dim3(NB_WAVES * 64), ctrl_node_bwd_lds(), st, b); };
+  return by_dim(a->dim, [&](auto D) {
+    if (a->a_max != 0.f)      // the actuator limit: its own instantiations
+      return b.coop ? go(ctrl_node_bwd_coop_lim_kernel<D()>) : go(ctrl_node_bwd_lim_kernel<D()>);
+    return b.coop ? go(ctrl_node_bwd_coop_kernel<D()>) : go(ctrl_node_bwd_kernel<D()>);
+  });
 }
-
-
 
 extern "C" int MB_SYM(ctrl_edge_bwd)(const mb::CtrlEdgeBwdArgs* a, int num_blocks, hipStream_t st) {
   using namespace mb;
@@ -2505,26 +2435,14 @@ extern "C" int MB_SYM(ctrl_edge_bwd)(const mb::CtrlEdgeBwdArgs* a, int num_block
   if (a->K > 16 || a->K < 1) return -1;
   if (a->w16) {   // 16x16x32 kernel (csrc/ctrl16.h; K = 12)
     if (a->K != 12) return -7;
-    if (a->dim == 3) launch_ctrl_edge_bwd16<3>(*a, num_blocks, st);
-    else launch_ctrl_edge_bwd16<2>(*a, num_blocks, st);
-    return (int)hipGetLastError();
+    return by_dim(a->dim, [&](auto D) { return launch_ctrl_edge_bwd16<D()>(*a, num_blocks, st); });
   }
-  const size_t lds = ctrl_edge_bwd_lds();
   // K = 12 (TOP_K): constant-K instantiation (A/B vs runtime K: 136.7 vs 137.1-139.6 us, PERF.md)
-  constexpr bool k12_off = false;
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(num_blocks), dim3(EB_WAVES * 64), lds, st, *a);
-  };
-  const bool k12 = a->K == 12 && !k12_off;
-  if (a->dim == 3) {
-    if (k12) go(ctrl_edge_bwd_kernel<3, 12>);
-    else go(ctrl_edge_bwd_kernel<3>);
-  } else {
-    if (k12) go(ctrl_edge_bwd_kernel<2, 12>);
-    else go(ctrl_edge_bwd_kernel<2>);
-  }
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) {
+    return by_k12(a->K, [&](auto KC) {
+      return launch_lds(ctrl_edge_bwd_kernel<D(), KC()>, dim3(num_blocks), dim3(EB_WAVES * 64), ctrl_edge_bwd_lds(), st, *a);
+    });
+  });
 }
 
 // One BPTT step in one launch for the cooperative regime (32-agent chunks: strong-scaling slices):
@@ -2544,27 +2462,13 @@ extern "C" int MB_SYM(ctrl_bwd_step)(const mb::CtrlNodeBwdArgs* na, const mb::Ct
   n.coop = 1;
   CtrlEdgeBwdArgs e = *ea;
   e.qsplit = 1;
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(num_blocks), dim3(NB_WAVES * 64), lds, st, n, e);
-  };
-  const bool k12 = ea->K == 12;
-  if (na->a_max != 0.f) {      // the actuator limit: its own instantiations
-    if (ea->dim == 3) {
-      if (k12) go(ctrl_bwd_step_lim_kernel<3, 12>);
-      else go(ctrl_bwd_step_lim_kernel<3, 0>);
-    } else {
-      if (k12) go(ctrl_bwd_step_lim_kernel<2, 12>);
-      else go(ctrl_bwd_step_lim_kernel<2, 0>);
-    }
-  } else if (ea->dim == 3) {
-    if (k12) go(ctrl_bwd_step_kernel<3, 12>);
-    else go(ctrl_bwd_step_kernel<3, 0>);
-  } else {
-    if (k12) go(ctrl_bwd_step_kernel<2, 12>);
-    else go(ctrl_bwd_step_kernel<2, 0>);
-  }
-  return (int)hipGetLastError();
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(num_blocks), dim3(NB_WAVES * 64), lds, st, n, e); };
+  return by_dim(ea->dim, [&](auto D) {
+    return by_k12(ea->K, [&](auto KC) {
+      if (na->a_max != 0.f) return go(ctrl_bwd_step_lim_kernel<D(), KC()>);      // the actuator limit: its own instantiations
+      return go(ctrl_bwd_step_kernel<D(), KC()>);
+    });
+  });
 }
 
 extern "C" int MB_SYM(rollout_small)(const mb::RolloutSmallArgs* a, hipStream_t st) {
@@ -2574,26 +2478,11 @@ extern "C" int MB_SYM(rollout_small)(const mb::RolloutSmallArgs* a, hipStream_t 
   if (c.K > 16 || c.K < 1 || c.N < 1 || a->Nn < c.N || a->Nn > SMALL_MAXN || c.K > a->Nn || a->Tmax < 1) return -1;
   if (!a->ctl || !a->idx || !a->dang || !a->cnt || !c.pooled || !c.argmax || !c.dist_sum || !c.S) return -2;
   if (c.apw < 2 || c.apw > 32 || (c.apw & 1)) return -3;
-  const size_t lds = rollout_small_lds();
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(c.B), dim3(SR_WAVES * 64), lds, st, *a);
-  };
-  if (c.a_max != 0.f) {
-    if (c.dim == 3) {
-      if (c.acts) go(rollout_small_lim_kernel<3, true>);
-      else go(rollout_small_lim_kernel<3, false>);
-    } else {
-      if (c.acts) go(rollout_small_lim_kernel<2, true>);
-      else go(rollout_small_lim_kernel<2, false>);
-    }
-  } else if (c.dim == 3) {
-    if (c.acts) go(rollout_small_kernel<3, true>);
-    else go(rollout_small_kernel<3, false>);
-  } else {
-    if (c.acts) go(rollout_small_kernel<2, true>);
-    else go(rollout_small_kernel<2, false>);
-  }
-  return (int)hipGetLastError();
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(c.B), dim3(SR_WAVES * 64), rollout_small_lds(), st, *a); };
+  return by_dim(c.dim, [&](auto D) {
+    return by_flag(c.acts != nullptr, [&](auto ACTS) {
+      if (c.a_max != 0.f) return go(rollout_small_lim_kernel<D(), ACTS()>);
+      return go(rollout_small_kernel<D(), ACTS()>);
+    });
+  });
 }
-

@@ -313,13 +313,10 @@ __global__ __launch_bounds__(E16_NW * 64, 2 * E16_WG_PER_CU) void ctrl_edge_bwd1
 }
 
 template <int D>
-static void launch_ctrl_edge_bwd16(const CtrlEdgeBwdArgs& a, int num_blocks, hipStream_t st) {
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)E16_LDS);
-    hipLaunchKernelGGL(kern, dim3(num_blocks), dim3(E16_NW * 64), E16_LDS, st, a);
-  };
-  if (a.stamps) go(ctrl_edge_bwd16_kernel<D, true>);
-  else go(ctrl_edge_bwd16_kernel<D, false>);
+static int launch_ctrl_edge_bwd16(const CtrlEdgeBwdArgs& a, int num_blocks, hipStream_t st) {
+  return by_flag(a.stamps != nullptr, [&](auto ST) {
+    return launch_lds(ctrl_edge_bwd16_kernel<D, ST()>, dim3(num_blocks), dim3(E16_NW * 64), E16_LDS, st, a);
+  });
 }
 
 }  // namespace MB_PREC

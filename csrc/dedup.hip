@@ -24,6 +24,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 
 namespace mb {
 
@@ -425,22 +426,19 @@ extern "C" int mb_cbf_compact(const float* dh, const int* nev, const int* blk_of
   if (!blk_off && !blk_active) return -1;
   if (rec && (!src || !idx)) return -2;
   if (!rec && !act) return -3;
-  hipLaunchKernelGGL(cbf_compact_kernel, dim3(num_blocks), dim3(DH_BLOCK), 0, st, dh, nev, blk_off, act, blk_active,
+  return mb::launch(cbf_compact_kernel, dim3(num_blocks), dim3(DH_BLOCK), 0, st, dh, nev, blk_off, act, blk_active,
                      nact, src, idx, idx1, E, (int4*)rec);
-  return (int)hipGetLastError();
 }
 
 extern "C" int mb_cbf_match(const mb::CbfMatchArgs* a, hipStream_t st) {
   using namespace mb;
   if (a->K < 1 || a->K > 16 || a->T < 1) return -1;
   const long rows = (long)a->T * a->B * a->N;
-  hipLaunchKernelGGL(cbf_match_kernel, dim3((unsigned)((rows + MATCH_BLOCK - 1) / MATCH_BLOCK)), dim3(MATCH_BLOCK),
+  return mb::launch(cbf_match_kernel, dim3((unsigned)((rows + MATCH_BLOCK - 1) / MATCH_BLOCK)), dim3(MATCH_BLOCK),
                      0, st, *a);
-  return (int)hipGetLastError();
 }
 
 extern "C" int mb_cbf_dh(const mb::CbfDhArgs* a, int num_blocks, hipStream_t st) {
   using namespace mb;
-  hipLaunchKernelGGL(cbf_dh_kernel, dim3(num_blocks), dim3(DH_BLOCK), 0, st, *a);
-  return (int)hipGetLastError();
+  return mb::launch(cbf_dh_kernel, dim3(num_blocks), dim3(DH_BLOCK), 0, st, *a);
 }

@@ -18,6 +18,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 #include "state.h"
 
 namespace mb {
@@ -235,9 +236,7 @@ extern "C" int mb_episode_limit(const mb::EpisodeArgs* a, hipStream_t st) {
   if ((long)a->B * a->N >= (1l << 31) - 65536) return -3;
   if (!a->A) return -2;
   const dim3 grid((unsigned)(((long)a->B * a->N * a->dim + EP_BLOCK - 1) / EP_BLOCK));
-  if (a->dim == 3) hipLaunchKernelGGL(episode_limit_kernel<3>, grid, dim3(EP_BLOCK), 0, st, *a);
-  else hipLaunchKernelGGL(episode_limit_kernel<2>, grid, dim3(EP_BLOCK), 0, st, *a);
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) { return launch(episode_limit_kernel<D()>, grid, dim3(EP_BLOCK), 0, st, *a); });
 }
 
 extern "C" int mb_episode_advance(const mb::EpisodeArgs* a, hipStream_t st) {
@@ -246,9 +245,7 @@ extern "C" int mb_episode_advance(const mb::EpisodeArgs* a, hipStream_t st) {
   if (!a->S_next || !a->A || !a->dist_fx || a->S_next == a->S_cur || (a->act_st && !a->active)) return -2;
   if (a->a_max < 0.f || a->a_max != a->a_max) return -1;
   const dim3 grid((unsigned)(((long)a->B * a->N + EP_BLOCK - 1) / EP_BLOCK));
-  if (a->dim == 3) hipLaunchKernelGGL(episode_advance_kernel<3>, grid, dim3(EP_BLOCK), 0, st, *a);
-  else hipLaunchKernelGGL(episode_advance_kernel<2>, grid, dim3(EP_BLOCK), 0, st, *a);
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) { return launch(episode_advance_kernel<D()>, grid, dim3(EP_BLOCK), 0, st, *a); });
 }
 
 extern "C" int mb_episode_tally(const mb::EpisodeArgs* a, hipStream_t st) {
@@ -256,15 +253,12 @@ extern "C" int mb_episode_tally(const mb::EpisodeArgs* a, hipStream_t st) {
   if (const int rc = episode_check(a)) return rc;
   if (!a->dist_fx || !a->active || a->loops < 0 || a->mode < 0 || a->mode > 2) return -2;
   if ((a->mode == 1 && !a->ctl) || (a->mode == 2 && !a->ew)) return -2;
-  hipLaunchKernelGGL(episode_tally_kernel, dim3(1), dim3(EP_BLOCK), 0, st, *a);
-  return (int)hipGetLastError();
+  return launch(episode_tally_kernel, dim3(1), dim3(EP_BLOCK), 0, st, *a);
 }
 
 extern "C" int mb_episode_final(const mb::EpisodeArgs* a, hipStream_t st) {
   using namespace mb;
   if (const int rc = episode_check(a)) return rc;
   if (!a->out) return -2;
-  if (a->dim == 3) hipLaunchKernelGGL(episode_final_kernel<3>, dim3(1), dim3(EP_BLOCK), 0, st, *a);
-  else hipLaunchKernelGGL(episode_final_kernel<2>, dim3(1), dim3(EP_BLOCK), 0, st, *a);
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) { return launch(episode_final_kernel<D()>, dim3(1), dim3(EP_BLOCK), 0, st, *a); });
 }

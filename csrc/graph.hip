@@ -9,6 +9,7 @@
 // (one workgroup per graph, LDS counting sort).
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 #include "state.h"
 #include "combine.h"
 
@@ -372,20 +373,13 @@ extern "C" int mb_rev_csr(const mb::CsrArgs* a, hipStream_t st) {
   const size_t lds_sorted = base + (size_t)NK * 2;
   const size_t lds_reg = base + (size_t)NK * 2;
   // (small graphs keep the 256-thread kernel: 32 x 12 edges, config #2, 18 vs 28 us per launch)
-  if (NK >= 4096 && NK <= CSR_JM * CSR_RB && lds_reg <= 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)rev_csr_reg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg);
-    hipLaunchKernelGGL(rev_csr_reg_kernel, dim3(a->G), dim3(CSR_RB), lds_reg, st, *a);
-  } else if (NK <= 65536 && lds_sorted <= 150 * 1024) {
-    (void)hipFuncSetAttribute((const void*)rev_csr_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sorted);
-    hipLaunchKernelGGL(rev_csr_kernel<true>, dim3(a->G), dim3(CSR_BLOCK), lds_sorted, st, *a);
-  } else if (base <= 150 * 1024) {
-    (void)hipFuncSetAttribute((const void*)rev_csr_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)base);
-    hipLaunchKernelGGL(rev_csr_kernel<false>, dim3(a->G), dim3(CSR_BLOCK), base, st, *a);
-  } else {
-    if (!a->ws) return -2;                       // global path: the caller provides (G, Nn) ints
-    hipLaunchKernelGGL(rev_csr_glb_kernel, dim3(a->G), dim3(CSR_BLOCK), 0, st, *a);
-  }
-  return (int)hipGetLastError();
+  if (NK >= 4096 && NK <= CSR_JM * CSR_RB && lds_reg <= 64 * 1024)
+    return launch_lds(rev_csr_reg_kernel, dim3(a->G), dim3(CSR_RB), lds_reg, st, *a);
+  if (NK <= 65536 && lds_sorted <= 150 * 1024)
+    return launch_lds(rev_csr_kernel<true>, dim3(a->G), dim3(CSR_BLOCK), lds_sorted, st, *a);
+  if (base <= 150 * 1024) return launch_lds(rev_csr_kernel<false>, dim3(a->G), dim3(CSR_BLOCK), base, st, *a);
+  if (!a->ws) return -2;                         // global path: the caller provides (G, Nn) ints
+  return launch(rev_csr_glb_kernel, dim3(a->G), dim3(CSR_BLOCK), 0, st, *a);
 }
 
 extern "C" int mb_node_reduce(const mb::NodeRedArgs* a, hipStream_t st) {
@@ -393,15 +387,11 @@ extern "C" int mb_node_reduce(const mb::NodeRedArgs* a, hipStream_t st) {
   const int t_hi = a->t_hi ? a->t_hi : a->T + 1;
   if (a->t_lo < 0 || t_hi > a->T + 1 || a->t_lo >= t_hi) return -1;
   const long total = (long)a->B * (t_hi - a->t_lo) * a->N * NRL;
-  if (a->dim == 3) hipLaunchKernelGGL(node_reduce_kernel<3>, dim3((total + 255) / 256), dim3(256), 0, st, *a);
-  else hipLaunchKernelGGL(node_reduce_kernel<2>, dim3((total + 255) / 256), dim3(256), 0, st, *a);
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) { return launch(node_reduce_kernel<D()>, dim3((total + 255) / 256), dim3(256), 0, st, *a); });
 }
 
 extern "C" int mb_node_combine(const mb::CombineArgs* a, hipStream_t st) {
   using namespace mb;
   const long total = (long)a->B * a->N * RG;
-  if (a->dim == 3) hipLaunchKernelGGL(node_combine_kernel<3>, dim3((total + 255) / 256), dim3(256), 0, st, *a);
-  else hipLaunchKernelGGL(node_combine_kernel<2>, dim3((total + 255) / 256), dim3(256), 0, st, *a);
-  return (int)hipGetLastError();
+  return by_dim(a->dim, [&](auto D) { return launch(node_combine_kernel<D()>, dim3((total + 255) / 256), dim3(256), 0, st, *a); });
 }

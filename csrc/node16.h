@@ -531,14 +531,10 @@ __global__ __launch_bounds__(N16_NW * 64) void ctrl_node_bwd16_kernel(CtrlNodeBw
 }
 
 template <int D>
-static void launch_ctrl_node_bwd16(const CtrlNodeBwdArgs& a, int num_blocks, hipStream_t st) {
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)N16_LDS);
-    hipLaunchKernelGGL(kern, dim3(num_blocks), dim3(N16_NW * 64), N16_LDS, st, a);
-  };
-  if (a.a_max != 0.f) go(ctrl_node_bwd16_kernel<D | N16_LIM, false>);      // (no phase clocks under the limit)
-  else if (a.stamps) go(ctrl_node_bwd16_kernel<D, true>);
-  else go(ctrl_node_bwd16_kernel<D, false>);
+static int launch_ctrl_node_bwd16(const CtrlNodeBwdArgs& a, int num_blocks, hipStream_t st) {
+  auto go = [&](auto kern) { return launch_lds(kern, dim3(num_blocks), dim3(N16_NW * 64), N16_LDS, st, a); };
+  if (a.a_max != 0.f) return go(ctrl_node_bwd16_kernel<D | N16_LIM, false>);      // (no phase clocks under the limit)
+  return by_flag(a.stamps != nullptr, [&](auto ST) { return go(ctrl_node_bwd16_kernel<D, ST()>); });
 }
 
 }  // namespace MB_PREC

@@ -4,6 +4,7 @@
 // of the single flat fp32 master buffer.
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 
 namespace mb {
 
@@ -342,16 +343,14 @@ extern "C" int mb_pack_gather(const float* src, int n, const int* idx16, int m16
   const int tot = m16 + m32;
   StepCommitArgs c{};
   if (commit) c = *commit;
-  hipLaunchKernelGGL(pack_gather_kernel, dim3(tot > 0 ? (tot + 255) / 256 : 1), dim3(256), 0, st, src, n, idx16, m16,
+  return mb::launch(pack_gather_kernel, dim3(tot > 0 ? (tot + 255) / 256 : 1), dim3(256), 0, st, src, n, idx16, m16,
                      out16, f16, idx32, m32, out32, c);
-  return (int)hipGetLastError();
 }
 
 extern "C" int mb_grad_assemble(const mb::GradAssembleArgs* a, hipStream_t st) {
   using namespace mb;
   const int blocks = (a->n + 255) / 256 + (a->row ? 1 : 0);
-  hipLaunchKernelGGL(grad_assemble_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, *a);
-  return (int)hipGetLastError();
+  return mb::launch(grad_assemble_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, *a);
 }
 
 extern "C" int mb_reduce_multi(const mb::ReduceMultiArgs* a, hipStream_t st) {
@@ -364,8 +363,7 @@ extern "C" int mb_reduce_multi(const mb::ReduceMultiArgs* a, hipStream_t st) {
     b.blk0[j] = blk;
     blk += (b.cols[j] / 4 + RR_COLS - 1) / RR_COLS;
   }
-  hipLaunchKernelGGL(reduce_multi_kernel, dim3(blk), dim3(RR_COLS * RR_SLICES), 0, st, b);
-  return (int)hipGetLastError();
+  return mb::launch(reduce_multi_kernel, dim3(blk), dim3(RR_COLS * RR_SLICES), 0, st, b);
 }
 
 extern "C" int mb_adam_multi(const mb::AdamMultiArgs* a, hipStream_t st) {
@@ -379,46 +377,39 @@ extern "C" int mb_adam_multi(const mb::AdamMultiArgs* a, hipStream_t st) {
     blk += n > 0 ? (n + 255) / 256 : 0;
   }
   if (blk == 0) return 0;
-  hipLaunchKernelGGL(adam_multi_kernel, dim3(blk), dim3(256), 0, st, b);
-  return (int)hipGetLastError();
+  return mb::launch(adam_multi_kernel, dim3(blk), dim3(256), 0, st, b);
 }
 
 extern "C" int mb_grad_check(const float* g, int n, int* ok, hipStream_t st) {
   using namespace mb;
   const int blocks = (n + 255) / 256 < 256 ? (n + 255) / 256 : 256;
-  hipLaunchKernelGGL(grad_check_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, g, n, ok);
-  return (int)hipGetLastError();
+  return mb::launch(grad_check_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, g, n, ok);
 }
 
 extern "C" int mb_step_commit(const mb::StepCommitArgs* a, hipStream_t st) {
   using namespace mb;
-  hipLaunchKernelGGL(step_commit_kernel, dim3(1), dim3(64), 0, st, *a);
-  return (int)hipGetLastError();
+  return mb::launch(step_commit_kernel, dim3(1), dim3(64), 0, st, *a);
 }
 
 extern "C" int mb_stats_pack(const float* sums, const float* counts, const float* local, float* row, hipStream_t st) {
   using namespace mb;
-  hipLaunchKernelGGL(stats_pack_kernel, dim3(1), dim3(64), 0, st, sums, counts, local, row);
-  return (int)hipGetLastError();
+  return mb::launch(stats_pack_kernel, dim3(1), dim3(64), 0, st, sums, counts, local, row);
 }
 
 extern "C" int mb_rollout_stats(const mb::RolloutStatsArgs* a, hipStream_t st) {
   using namespace mb;
-  hipLaunchKernelGGL(rollout_stats_kernel, dim3(1), dim3(RS_BLOCK), 0, st, *a);
-  return (int)hipGetLastError();
+  return mb::launch(rollout_stats_kernel, dim3(1), dim3(RS_BLOCK), 0, st, *a);
 }
 
 extern "C" int mb_reduce_rows(const float* partial, int rows, int cols, float* out, int accumulate, hipStream_t st) {
   if (cols % 4) return -1;
   const int groups = cols / 4;
-  hipLaunchKernelGGL(mb::reduce_rows_kernel, dim3((groups + mb::RR_COLS - 1) / mb::RR_COLS),
+  return mb::launch(mb::reduce_rows_kernel, dim3((groups + mb::RR_COLS - 1) / mb::RR_COLS),
                      dim3(mb::RR_COLS * mb::RR_SLICES), 0, st, partial, rows, cols, out, accumulate);
-  return (int)hipGetLastError();
 }
 
 extern "C" int mb_adam(const mb::AdamArgs* a, hipStream_t st) {
   const int n = a->hi - a->lo;
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(mb::adam_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *a);
-  return (int)hipGetLastError();
+  return mb::launch(mb::adam_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *a);
 }

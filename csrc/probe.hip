@@ -1,6 +1,7 @@
 // Layout probes: check on the device the MFMA operand/accumulator maps and the
 // ds_read_b64_tr_b16 transposed-read semantics that the fused kernels are built on.
 #include "common.h"
+#include "launch.h"
 
 namespace mb {
 
@@ -85,30 +86,24 @@ __global__ __launch_bounds__(512) void probe_mfma_exec_kernel(const h16* a, floa
 }  // namespace mb
 
 extern "C" int mb_probe_mfma_exec(const void* a, float* out, int uniform, hipStream_t st) {
-  if (uniform)
-    hipLaunchKernelGGL(mb::probe_mfma_exec_kernel<true>, dim3(1), dim3(512), 0, st, (const h16*)a, out);
-  else
-    hipLaunchKernelGGL(mb::probe_mfma_exec_kernel<false>, dim3(1), dim3(512), 0, st, (const h16*)a, out);
-  return (int)hipGetLastError();
+  return mb::by_flag(uniform != 0, [&](auto U) {
+    return mb::launch(mb::probe_mfma_exec_kernel<U()>, dim3(1), dim3(512), 0, st, (const h16*)a, out);
+  });
 }
 
 extern "C" int mb_probe_lane_xor(const unsigned* in, unsigned* out, hipStream_t st) {
-  hipLaunchKernelGGL(mb::probe_lane_xor_kernel, dim3(1), dim3(64), 0, st, in, out);
-  return (int)hipGetLastError();
+  return mb::launch(mb::probe_lane_xor_kernel, dim3(1), dim3(64), 0, st, in, out);
 }
 
 extern "C" int mb_probe_mfma16(const void* a, const void* b, float* d, hipStream_t st) {
-  hipLaunchKernelGGL(mb::probe_mfma16_kernel, dim3(1), dim3(64), 0, st, (const h16*)a, (const h16*)b, d);
-  return (int)hipGetLastError();
+  return mb::launch(mb::probe_mfma16_kernel, dim3(1), dim3(64), 0, st, (const h16*)a, (const h16*)b, d);
 }
 
 extern "C" int mb_probe_mfma(const void* a, const void* b, float* d, hipStream_t st) {
-  hipLaunchKernelGGL(mb::probe_mfma_kernel, dim3(1), dim3(64), 0, st, (const h16*)a, (const h16*)b, d);
-  return (int)hipGetLastError();
+  return mb::launch(mb::probe_mfma_kernel, dim3(1), dim3(64), 0, st, (const h16*)a, (const h16*)b, d);
 }
 
 extern "C" int mb_probe_tr(const void* img, int rows, int stride, int e0, int m0, void* out, hipStream_t st) {
   if (rows * stride > 64 * 136) return -1;
-  hipLaunchKernelGGL(mb::probe_tr_kernel, dim3(1), dim3(64), 0, st, (const h16*)img, rows, stride, e0, m0, (h16*)out);
-  return (int)hipGetLastError();
+  return mb::launch(mb::probe_tr_kernel, dim3(1), dim3(64), 0, st, (const h16*)img, rows, stride, e0, m0, (h16*)out);
 }

@@ -32,6 +32,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 #include "state.h"
 #include "cbf_edge.h"
 #include "combine.h"
@@ -458,20 +459,18 @@ __global__ __launch_bounds__(NW * 64, 1) void refine_small_kernel(RefineSmallArg
   for (int x = tid; x < N * D; x += nthr) dg[x] = dl[x];
 }
 
-template <int D>
-static void launch_refine_grad(const RefineArgs& a, int num_blocks, hipStream_t st) {
-  hipLaunchKernelGGL((refine_grad_kernel<REFINE_NW, D>), dim3(num_blocks), dim3(REFINE_NW * 64), REFINE_LDS, st, a);
-}
-
 }  // namespace MB_PREC
 }  // namespace mb
 
 // once per loop, before the first refine_grad launch: the kernel's dynamic LDS exceeds the default limit
 extern "C" int MB_SYM(refine_prepare)(int dim) {
+  using namespace mb;
   using namespace mb::MB_PREC;
   if (dim != 2 && dim != 3) return -1;
-  const void* f = dim == 3 ? (const void*)refine_grad_kernel<REFINE_NW, 3> : (const void*)refine_grad_kernel<REFINE_NW, 2>;
-  return (int)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)REFINE_LDS);
+  return by_dim(dim, [](auto D) {
+    return (int)hipFuncSetAttribute((const void*)refine_grad_kernel<REFINE_NW, D()>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)REFINE_LDS);
+  });
 }
 
 extern "C" int MB_SYM(refine_grad)(const mb::RefineArgs* a, int num_blocks, hipStream_t st) {
@@ -480,10 +479,10 @@ extern "C" int MB_SYM(refine_grad)(const mb::RefineArgs* a, int num_blocks, hipS
   if (a->K > 16 || a->K < 1 || a->B < 1 || a->N < 1 || a->Nn < a->N || num_blocks < 1 || a->it < 0) return -1;
   if (!a->S || !a->idx || !a->a || !a->delta || !a->h || !a->wpack || !a->wrm || !a->wvec || !a->dEv || !a->ctl) return -2;
   if ((long)a->B * a->N * a->K >= (1l << 31) - 32l * 65536) return -3;     // 32-bit edge indexing
-  if (a->dim == 3) launch_refine_grad<3>(*a, num_blocks, st);
-  else if (a->dim == 2) launch_refine_grad<2>(*a, num_blocks, st);
-  else return -1;
-  return (int)hipGetLastError();
+  if (a->dim != 2 && a->dim != 3) return -1;
+  return by_dim(a->dim, [&](auto D) {     // (the LDS attribute: refine_prepare, once per loop)
+    return launch(refine_grad_kernel<REFINE_NW, D()>, dim3(num_blocks), dim3(REFINE_NW * 64), REFINE_LDS, st, *a);
+  });
 }
 
 // The persistent filter of envs of at most RS_MAXN graph nodes: one launch of B workgroups. Sets
@@ -497,15 +496,14 @@ extern "C" int MB_SYM(refine_small)(const mb::RefineSmallArgs* sa, hipStream_t s
       !sa->ew)
     return -2;
   if (a->s_env < a->Nn) return -1;
-  auto go = [&](auto kern, size_t lds) {
+  if (a->dim != 2 && a->dim != 3) return -1;
+  return by_dim(a->dim, [&](auto D) {
+    const auto kern = refine_small_kernel<REFINE_NW, D()>;
+    const size_t lds = REFINE_SMALL_LDS<REFINE_NW, D()>;
     const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(a->B), dim3(REFINE_NW * 64), lds, st, *sa);
-    return (int)hipGetLastError();
-  };
-  if (a->dim == 3) return go(refine_small_kernel<REFINE_NW, 3>, REFINE_SMALL_LDS<REFINE_NW, 3>);
-  if (a->dim == 2) return go(refine_small_kernel<REFINE_NW, 2>, REFINE_SMALL_LDS<REFINE_NW, 2>);
-  return -1;
+    if (e != hipSuccess) return (int)e;     // this launcher reports the attribute's error
+    return launch(kern, dim3(a->B), dim3(REFINE_NW * 64), lds, st, *sa);
+  });
 }
 
 #if !MB_X3 && !MB_FP16
@@ -543,9 +541,7 @@ extern "C" int mb_refine_update(const mb::RefineArgs* a, hipStream_t st) {
   if (!a->delta || !a->dEv || !a->ptr || !a->edges || !a->ctl || (a->a_max > 0.f && !a->a)) return -2;
   const long total = (long)a->B * a->N * RG;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (a->dim == 3) hipLaunchKernelGGL(refine_update_kernel<3>, grid, dim3(256), 0, st, *a);
-  else if (a->dim == 2) hipLaunchKernelGGL(refine_update_kernel<2>, grid, dim3(256), 0, st, *a);
-  else return -1;
-  return (int)hipGetLastError();
+  if (a->dim != 2 && a->dim != 3) return -1;
+  return by_dim(a->dim, [&](auto D) { return launch(refine_update_kernel<D()>, grid, dim3(256), 0, st, *a); });
 }
 #endif

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 #include "state.h"
 #include "ttc.h"
 
@@ -972,37 +973,29 @@ static ScanPlan plan_kdb(const ScanArgs& a) {
 }
 
 template <int K, int D, int BS, int LPA = SCAN_LPA>
-static void launch_kdb(const ScanArgs& a, hipStream_t st, ScanPlan* plan) {
+static int launch_kdb(const ScanArgs& a, hipStream_t st, ScanPlan* plan) {
   const ScanPlan p = plan_kdb<D, BS, LPA>(a);
   if (plan) {                // mb_scan_plan: report, do not launch
     *plan = p;
-    return;
+    return 0;
   }
-  dim3 grid((a.Nn + BS / LPA - 1) / (BS / LPA), a.B);
+  const dim3 grid((a.Nn + BS / LPA - 1) / (BS / LPA), a.B), block(BS);
   if (p.glb) {
     const int Np = (a.Nn + SCH - 1) / SCH * SCH, nch = Np / SCH;
-    hipLaunchKernelGGL(scan_stage_kernel<D>, dim3((nch + STAGE_BLOCK - 1) / STAGE_BLOCK, a.B), dim3(STAGE_BLOCK), 0,
-                       st, a);
+    const int rc = launch(scan_stage_kernel<D>, dim3((nch + STAGE_BLOCK - 1) / STAGE_BLOCK, a.B), dim3(STAGE_BLOCK), 0, st, a);
+    if (rc) return rc;
     if (p.glb == 2) {                // huge envs: the boxes stay in the global workspace
-      if constexpr (BS == SCAN_BS_BIG && LPA == SCAN_LPA)
-        hipLaunchKernelGGL((scan_kernel<K, D, BS, LPA, 2>), grid, dim3(BS), 0, st, a);
-      return;
+      if constexpr (BS == SCAN_BS_BIG && LPA == SCAN_LPA) return launch(scan_kernel<K, D, BS, LPA, 2>, grid, block, 0, st, a);
+      return 0;
     }
-    (void)hipFuncSetAttribute((const void*)scan_kernel<K, D, BS, LPA, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-    hipLaunchKernelGGL((scan_kernel<K, D, BS, LPA, 1>), grid, dim3(BS), p.lds, st, a);
-    return;
+    return launch_lds(scan_kernel<K, D, BS, LPA, 1>, grid, block, p.lds, st, a);
   }
   ScanArgs b = a;
   b.cells = p.cells;
-  if constexpr (K == 12) {
-    if (a.stamps) {           // diagnostics: phase clocks (scripts/stamps_scan.py)
-      (void)hipFuncSetAttribute((const void*)scan_kernel<K, D, BS, LPA, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-      hipLaunchKernelGGL((scan_kernel<K, D, BS, LPA, 0, true>), grid, dim3(BS), p.lds, st, b);
-      return;
-    }
-  }
-  (void)hipFuncSetAttribute((const void*)scan_kernel<K, D, BS, LPA, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-  hipLaunchKernelGGL((scan_kernel<K, D, BS, LPA, 0>), grid, dim3(BS), p.lds, st, b);
+  if constexpr (K == 12)
+    if (a.stamps)             // diagnostics: phase clocks (scripts/stamps_scan.py)
+      return launch_lds(scan_kernel<K, D, BS, LPA, 0, true>, grid, block, p.lds, st, b);
+  return launch_lds(scan_kernel<K, D, BS, LPA, 0>, grid, block, p.lds, st, b);
 }
 
 
@@ -1049,25 +1042,23 @@ static bool scan_boxes_global(const ScanArgs& a) {
 // pass, 8-env slice 2.826 / 2.829 vs 2.830 / 2.809 ms, neutral; removed, profiles/r6c/)
 
 template <int K, int D>
-static void launch_kd(const ScanArgs& a, hipStream_t st, ScanPlan* plan) {
-  if (scan_boxes_global(a)) launch_kdb<K, D, SCAN_BS_BIG>(a, st, plan);
-  else if (scan_lpa8(a)) launch_kdb<K, D, 256, 8>(a, st, plan);
-  else if (a.Nn > 512 && !scan_small_grid<D>(a)) launch_kdb<K, D, D == 3 ? SCAN_BS_BIG3 : SCAN_BS_BIG>(a, st, plan);
-  else launch_kdb<K, D, 256>(a, st, plan);
+static int launch_kd(const ScanArgs& a, hipStream_t st, ScanPlan* plan) {
+  if (scan_boxes_global(a)) return launch_kdb<K, D, SCAN_BS_BIG>(a, st, plan);
+  if (scan_lpa8(a)) return launch_kdb<K, D, 256, 8>(a, st, plan);
+  if (a.Nn > 512 && !scan_small_grid<D>(a)) return launch_kdb<K, D, D == 3 ? SCAN_BS_BIG3 : SCAN_BS_BIG>(a, st, plan);
+  return launch_kdb<K, D, 256>(a, st, plan);
 }
 
 template <int K>
-static void launch_k(const ScanArgs& a, hipStream_t st, ScanPlan* plan = nullptr) {
-  if (a.dim == 3) launch_kd<K, 3>(a, st, plan);
-  else launch_kd<K, 2>(a, st, plan);
+static int launch_k(const ScanArgs& a, hipStream_t st, ScanPlan* plan = nullptr) {
+  return by_dim(a.dim, [&](auto D) { return launch_kd<K, D()>(a, st, plan); });
 }
 
 }  // namespace mb
 
 extern "C" int mb_cell_sort(const mb::CellSortArgs* a, hipStream_t st) {
   using namespace mb;
-  hipLaunchKernelGGL(cell_sort_kernel, dim3(a->B), dim3(SORT_BLOCK), 0, st, *a);
-  return (int)hipGetLastError();
+  return launch(cell_sort_kernel, dim3(a->B), dim3(SORT_BLOCK), 0, st, *a);
 }
 
 extern "C" int mb_scan(const mb::ScanArgs* a, hipStream_t st) {
@@ -1078,13 +1069,12 @@ extern "C" int mb_scan(const mb::ScanArgs* a, hipStream_t st) {
     if (!a->ws || a->ws_env < 2L * Np + 2L * (nch + nsc)) return -4;
   }
   switch (a->do_knn ? a->K : 1) {
-#define CASE(k) case k: launch_k<k>(*a, st); break;
+#define CASE(k) case k: return launch_k<k>(*a, st);
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
     CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16)
 #undef CASE
     default: return -1;
   }
-  return (int)hipGetLastError();
 }
 
 // The plan mb_scan would launch for these arguments (no launch; the plan does not depend on K):

@@ -13,6 +13,7 @@
 // (acceptance is order independent); its round barriers carry agent-scope fences (round_sync).
 #include "common.h"
 #include "args.h"
+#include "launch.h"
 #include "state.h"
 
 // no fp contraction: proposals and distance tests round exactly like the host runtime
@@ -205,12 +206,5 @@ extern "C" int mb_scenario(const mb::ScenArgs* a, hipStream_t st) {
   }
   g.G = G;
   g.inv = (float)G / span;
-  if (D == 3) {
-    (void)hipFuncSetAttribute((const void*)scenario_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(scenario_kernel<3>, dim3(a->B), dim3(SC_BLOCK), lds, st, *a, g);
-  } else {
-    (void)hipFuncSetAttribute((const void*)scenario_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(scenario_kernel<2>, dim3(a->B), dim3(SC_BLOCK), lds, st, *a, g);
-  }
-  return (int)hipGetLastError();
+  return by_dim(D, [&](auto DC) { return launch_lds(scenario_kernel<DC()>, dim3(a->B), dim3(SC_BLOCK), lds, st, *a, g); });
 }
