@@ -9,6 +9,10 @@ node kernel (every precision, csrc/node16.h) against the 32x32x16 node kernel --
 docs/ARCHITECTURE.md "Scheduling boundary") then stops training instead of corrupting it
 (ADVICE r3). MACBF_SELFCHECK=0 skips it.
 
+`node_oracle` is the same for one controller node-backward call (csrc/node16.h and the three bodies
+of csrc/ctrl.hip; tests/test_gpu_node_oracle.py pins them to it, tests/test_node_oracle_ref.py pins
+it to autograd through oracle.controller_forward). The start-up check does not call it yet.
+
 Tolerances. A row may deviate only on a provable relu / radius tie: some pre-activation
 |z| <= TAU * sum |terms| (TAU = 3e-5 is the x3 arithmetic's own bound: each product carries
 <= ~2^-16 relative error), or |d - R| <= 1e-6. Otherwise |kernel - float64| <= ROW_TOL |ref| +
@@ -160,6 +164,67 @@ def edge_oracle(p, S, idx, argmax, dP, N, D):
     s1 = (dz2 @ w2.detach().reshape(128, 64).abs()) * (z1.detach() > 0).double()
     rscale = (s1 @ w1.detach().reshape(64, -1)[:, :2 * D].abs()).reshape(B, N, K, 2 * D) * notself
     return drel, tie.reshape(B, N, K), dws, scales, rscale
+
+
+def node_oracle(p, pooled_hi, pooled_lo, S, G, A, Gn, valid, c, a_max=None):
+    """float64 autograd of ONE controller node-backward call (csrc/node16.h, csrc/ctrl.hip
+    node_bwd_body / node_bwd_coop / ctrl_bwd_step). Per agent, ex = p - g, x = [pooled, ex, v],
+    y = dec_net(x), k = 2 sigmoid(y) + 0.2, a_q = -(k_2q ex_q + k_2q+1 v_q), a_ref = -(ex + sqrt3 v):
+
+        L = sum_agents dt sum_q Gn_v[q] m_q a_q + c valid_b | |A^|^2 - |a_ref|^2 |
+
+    A^ has the value of the stored raw action A and the derivative of the recomputed a; m_q = 1, or
+    with a_max: 1 iff -a_max <= A_q <= a_max; c is the effective coefficient (act_coef / max(n_act, 1),
+    times the loss scale). pooled_hi (+ pooled_lo, x3) (B, N, 128); S, Gn (B, >= N, W) records; G, A
+    (B, N, D); valid (B,) or None. -> (dP rows (n, 128), ego rows (n, 2D) = dL/d[p, v] without the
+    Euler adjoint, dW dict, tie flags (n,), |term| scales dict (+ "@tie"), dP row scales, ego row
+    scales). The dec net goes through oracle._lin, so oracle.emulate_bf16 applies to it."""
+    from .. import oracle as O
+    B, N, D = G.shape
+    n = B * N
+    pl = pooled_hi[..., :128].detach().double()
+    if pooled_lo is not None:
+        pl = pl + pooled_lo[..., :128].detach().double()
+    pl = pl.reshape(n, 128).requires_grad_(True)
+    sv = native.from_records(S[:, :N].detach()).double().reshape(n, 2 * D).requires_grad_(True)
+    gnv = native.from_records(Gn[:, :N].detach()).double().reshape(n, 2 * D)[:, D:]       # only the velocity half enters
+    g = G.detach().double().reshape(n, D)
+    Af = A.detach().double().reshape(n, D)
+    vrow = (torch.ones(B, dtype=torch.float64, device=G.device) if valid is None
+            else (valid != 0).double()).repeat_interleave(N)
+    pr = {n_: v.detach().double().clone().requires_grad_(True) for n_, v in p.items()
+          if n_.startswith("controller_dec_net")}
+    ex, v = sv[:, :D] - g, sv[:, D:]
+    z = torch.cat([O._qg(O._qa(pl)), ex, v], -1)
+    tie = torch.zeros(n, dtype=torch.bool, device=G.device)
+    pres, ins = [], []
+    for li in (0, 2, 4, 6):
+        w, b = pr[f"controller_dec_net.{li}.weight"], pr[f"controller_dec_net.{li}.bias"]
+        pre = O._lin(z, w, b, first=li == 0)
+        ins.append(z.detach())
+        pres.append(pre)
+        if li != 6:
+            tie |= _tie(pre.detach(), z.detach(), w.detach(), b.detach())
+            z = F.relu(pre)
+    k = 2.0 * torch.sigmoid(pres[-1]) + 0.2
+    kp, kv = k[:, 0::2], k[:, 1::2]
+    a = -(kp * ex + kv * v)
+    ar = -(ex + C.SQRT3 * v)
+    m = torch.ones_like(Af) if not a_max else ((Af >= -a_max) & (Af <= a_max)).double()
+    ah = a + (Af - a).detach()
+    diff = (ah * ah).sum(-1) - (ar * ar).sum(-1)
+    loss = (C.TIME_STEP * (gnv * m * a).sum(-1)).sum() + (c * vrow * diff.abs()).sum()
+    grads = torch.autograd.grad(loss, [pl, sv, a] + list(pr.values()) + pres)
+    dws = dict(zip(pr.keys(), grads[3:3 + len(pr)]))
+    dzs = grads[3 + len(pr):]
+    w1 = pr["controller_dec_net.0.weight"].detach().abs()
+    dz1 = dzs[0].detach().abs()
+    da = grads[2].detach().abs()
+    cr = (c * vrow * (diff.detach() != 0).double()).abs().unsqueeze(-1) * 2.0 * ar.detach().abs()
+    pscale = dz1 @ w1[:, :128]
+    escale = dz1 @ w1[:, 128:] + torch.cat([kp.detach() * da + cr, kv.detach() * da + C.SQRT3 * cr], -1)
+    scales = abs_scales(pr, ins, dzs, "controller_dec_net", (0, 2, 4, 6), tie=tie)
+    return grads[0], grads[1], dws, tie, scales, pscale, escale
 
 
 def _params(fp, module):
