@@ -229,7 +229,13 @@ struct RefineArgs {
   // delta onto [-a_max - a, a_max - a], so a + delta stays in the box (up to the one rounding the
   // caller's final clamp removes)
   float a_max;
+  // decentralised filter (0: the joint filter): a neighbour slot uses the neighbour's nominal next
+  // state -- no delta_j unless j == i -- and the update sums the agent's own K slots alone (ptr and
+  // edges are then not read). Selects refine_grad_local_kernel / refine_update_local_kernel. (Sits in
+  // the struct's tail padding: the kernels' argument size does not change.)
+  int local;
 };
+static_assert(sizeof(RefineArgs) % 8 == 0, "RefineArgs layout");
 
 // Persistent safety filter for small envs (refine.hip refine_small_kernel): one workgroup per env
 // runs all `loops` iterations in one launch; r.dEv, r.ctl and r.it are not used.
@@ -507,6 +513,9 @@ int mb_refine_update(const mb::RefineArgs* a, hipStream_t st);
 int mb_refine_small(const mb::RefineSmallArgs* a, hipStream_t st);
 int mb_refine_small_f16(const mb::RefineSmallArgs* a, hipStream_t st);
 int mb_refine_small_x3(const mb::RefineSmallArgs* a, hipStream_t st);
+int mb_refine_local(const mb::RefineSmallArgs* a, int num_blocks, hipStream_t st);
+int mb_refine_local_f16(const mb::RefineSmallArgs* a, int num_blocks, hipStream_t st);
+int mb_refine_local_x3(const mb::RefineSmallArgs* a, int num_blocks, hipStream_t st);
 int mb_rev_csr(const mb::CsrArgs* a, hipStream_t st);
 int mb_cbf_match(const mb::CbfMatchArgs* a, hipStream_t st);
 int mb_cbf_dh(const mb::CbfDhArgs* a, int num_blocks, hipStream_t st);

@@ -61,7 +61,9 @@ struct RefIn {
 // neighbour slot, hv = h(s_t). Every load is unconditional on a clamped index (idx holds node ids
 // up to Nn - 1, a / delta have N rows: an obstacle neighbour reads row N - 1 and is zeroed). An edge
 // that is not in the tile (`in` false: past the end, or of a masked-out env) loads like any other.
-template <int D>
+// LOCAL (the decentralised filter): a neighbour's next state is its nominal one, s_j + dt [v_j, a_j];
+// only the self slot (j == i) carries the agent's own delta, so its relative state stays exactly zero.
+template <int D, bool LOCAL = false>
 DEV void refine_edge(const float4* Sb, const float* ab, const float* db, int jr, float hv, unsigned i, int N, int Nn,
                      float dt, bool in, RefIn<D>& x) {
   x.in = in;
@@ -79,7 +81,9 @@ DEV void refine_edge(const float4* Sb, const float* ab, const float* db, int jr,
 #pragma unroll
   for (int q = 0; q < D; ++q) {
     const float ui = ai[q] + di[q];
-    const float uj = agent_j ? aj[q] + dj[q] : 0.f;
+    float uj;
+    if constexpr (LOCAL) uj = agent_j ? (j == i ? aj[q] + dj[q] : aj[q]) : 0.f;
+    else uj = agent_j ? aj[q] + dj[q] : 0.f;
     // s' = s + [v, a + delta] * dt (the evaluation's own expression order)
     const float pin = pi[q] + vi[q] * dt, pjn = pj[q] + vj[q] * dt;
     const float vin = vi[q] + ui * dt, vjn = vj[q] + uj * dt;
@@ -91,7 +95,7 @@ DEV void refine_edge(const float4* Sb, const float* ab, const float* db, int jr,
 }
 
 // Edge e = (b*N + i)*K + k of a batch-wide tile. An edge of a masked-out env is marked as not in the tile.
-template <int D>
+template <int D, bool LOCAL = false>
 DEV void refine_load(const RefineArgs& a, unsigned tile, int r, unsigned E, RefIn<D>& x) {
   const unsigned e = tile * 32u + (unsigned)r;
   const bool inside = e < E;
@@ -100,8 +104,8 @@ DEV void refine_load(const RefineArgs& a, unsigned tile, int r, unsigned E, RefI
   const unsigned b = ik / (unsigned)a.N;
   const bool in = inside && (a.env_active ? a.env_active[b] != 0 : true);
   const unsigned i = ik - b * (unsigned)a.N;
-  refine_edge<D>(a.S + (size_t)b * (size_t)a.s_env * REC<D>, a.a + (size_t)b * a.N * D, a.delta + (size_t)b * a.N * D,
-                 a.idx[ec], a.h[ec], i, a.N, a.Nn, a.dt, in, x);
+  refine_edge<D, LOCAL>(a.S + (size_t)b * (size_t)a.s_env * REC<D>, a.a + (size_t)b * a.N * D,
+                        a.delta + (size_t)b * a.N * D, a.idx[ec], a.h[ec], i, a.N, a.Nn, a.dt, in, x);
 }
 
 // The weight images in LDS (the same layout in both kernels), copied by the whole workgroup; the
@@ -314,6 +318,44 @@ __global__ __launch_bounds__(NW * 64, 1) void refine_grad_kernel(RefineArgs a) {
   }
 }
 
+// The decentralised filter's loop path (a.local): refine_grad_kernel with the LOCAL loads, a kernel of
+// its own name -- the joint kernel keeps its own, instruction for instruction.
+template <int NW, int D>
+__global__ __launch_bounds__(NW * 64, 1) void refine_grad_local_kernel(RefineArgs a) {
+  // early-out: the previous iteration had no active edge -> nothing can change any more (this
+  // iteration's control words stay zero, which stops the next one)
+  if (a.it > 0 && a.ctl[2 * (a.it - 1)] == 0ull) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const RefW w = refine_weights(smem, a);
+  __syncthreads();
+  const int wave = wave_id(), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const unsigned E = (unsigned)a.B * a.N * a.K;
+  const unsigned ntiles = (E + 31u) / 32u;
+  const unsigned stride = gridDim.x * NW;
+  unsigned long long nact = 0, vsum = 0;
+  unsigned tile = (unsigned)blockIdx.x * NW + wave;
+  RefIn<D> nx;
+  refine_load<D, true>(a, tile, r, E, nx);
+  for (; tile < ntiles; tile += stride) {
+    const RefIn<D> cur = nx;
+    refine_load<D, true>(a, tile + stride, r, E, nx);   // prefetch (clamped past the end)
+    // no live edge (every env of the tile masked out): nothing to evaluate. One scalar branch on
+    // the ballot for the whole wave -- no MFMA below runs under a lane-divergent condition.
+    if (__ballot(cur.in) == 0ull) continue;
+    RefOut<D> o;
+    refine_tile<D>(cur, w, a, lane, h, o);
+    if (cur.in && h == 0) {
+      const size_t e = tile * 32u + (unsigned)r;
+      refine_record<D>(cur, o, a.hn_out, a.flag_out, e, a.dEv + e * D, nact, vsum);
+    }
+  }
+  const unsigned long long n = wave_sum_u64(nact), s = wave_sum_u64(vsum);
+  if (lane == 0) {
+    if (n) atomicAdd(a.ctl + 2 * a.it, n);
+    if (s) atomicAdd(a.ctl + 2 * a.it + 1, s);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Persistent filter for small envs (Nn <= SMALL_MAXN graph nodes, K <= 16: at most 32 tiles): one
 // workgroup per env runs the whole loop in one launch. Prologue: the weight images and the env's
@@ -345,18 +387,21 @@ static_assert(REFINE_LDS % 16 == 0 && REFINE_SMALL_LDS<REFINE_NW, 3> <= 128 * 10
 // one env's arrays (dE (N*K, D), ptr / edges its reverse CSR), the same value in all 16 lanes.
 // Outgoing edges: one coalesced segment of K records; incoming: the reverse CSR over the lanes;
 // then the fixed xor butterfly.
-template <int D>
+// LOCAL (the decentralised filter): the agent's own K slots alone -- no in-edge term, no reverse CSR.
+template <int D, bool LOCAL = false>
 DEV void refine_node_grad(const float* dE, const int* ptr, const int* edges, int i, int l, int K, int NK, float (&g)[D]) {
 #pragma unroll
   for (int q = 0; q < D; ++q) g[q] = 0.f;
   for (int k = l; k < K; k += RG)
 #pragma unroll
     for (int q = 0; q < D; ++q) g[q] += dE[((size_t)i * K + k) * D + q];
-  const int q0 = min(max(ptr[i], 0), NK), q1 = min(max(ptr[i + 1], 0), NK);
-  for (int x = q0 + l; x < q1; x += RG) {
-    const int e = min(max(edges[x], 0), NK - 1);
+  if constexpr (!LOCAL) {
+    const int q0 = min(max(ptr[i], 0), NK), q1 = min(max(ptr[i + 1], 0), NK);
+    for (int x = q0 + l; x < q1; x += RG) {
+      const int e = min(max(edges[x], 0), NK - 1);
 #pragma unroll
-    for (int q = 0; q < D; ++q) g[q] -= dE[(size_t)e * D + q];
+      for (int q = 0; q < D; ++q) g[q] -= dE[(size_t)e * D + q];
+    }
   }
 #pragma unroll
   for (int q = 0; q < D; ++q) g[q] = grp_sum(g[q]);
@@ -459,6 +504,142 @@ __global__ __launch_bounds__(NW * 64, 1) void refine_small_kernel(RefineSmallArg
   for (int x = tid; x < N * D; x += nthr) dg[x] = dl[x];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Decentralised filter (coupling "local"), the whole loop in one launch for any scene. Agent i refines
+// its own action against its neighbours' NOMINAL next states s_j + dt [v_j, a_j]: its problem depends
+// on its own row alone, so a wave keeps everything in registers. A 32-edge tile is 2 agents x 16 slots
+// (slots >= K are not in the tile, like the edges of a masked-out env; tiles straddle envs when N is
+// odd). The wave gathers s_i, s_j, a_i, a_j and h(s_t) once per tile -- the next tile's gathers are
+// issued before the current tile's loop, unconditionally on clamped indices -- and p'_i - p'_j and v'_j
+// are loop invariants. Per iteration: u_i = a_i + delta_i, v'_i and rv in refine_edge's expression
+// order (the self slot takes v'_j = v'_i: an exact zero), refine_tile unchanged, gv zeroed for self
+// and inactive edges, the 16 slots of an agent summed with refine_node_grad's butterfly (one term per
+// lane: the same pairing, the same bits), refine_step and refine_project. delta lives in registers and
+// is stored once. The tile stops at its first iteration without an active edge (a ballot, scalar: no
+// MFMA under a lane-divergent condition) and then adds the violation sum of its unchanged iterate to
+// every later word, as refine_small_kernel repeats its word. ctl is the loop path's array, zero at
+// the launch; integer atomics, so the result words do not depend on the order. The only barrier is
+// the one after the weight copy. hn_out / flag_out: iteration 0 only.
+template <int D>
+struct LocIn {
+  float pi[D], vi[D], pj[D], vj[D], ai[D], aj[D];
+  float hv;
+  unsigned g, e;        // the agent b*N + i and the edge g*K + k (clamped to 0 where there is none)
+  int i, j;
+  bool live, in, agent_j;   // live: the lane's agent exists in a live env; in: and its slot is < K
+};
+
+template <int D>
+DEV void refine_local_load(const RefineArgs& a, unsigned tile, int r, unsigned BN, LocIn<D>& x) {
+  const unsigned g = tile * 2u + (unsigned)(r >> 4);
+  const int k = r & 15;
+  const bool ag = g < BN;
+  const unsigned gc = ag ? g : 0u;
+  const unsigned b = gc / (unsigned)a.N;
+  const unsigned i = gc - b * (unsigned)a.N;
+  x.live = ag && (a.env_active ? a.env_active[b] != 0 : true);
+  x.in = x.live && k < a.K;
+  x.g = gc;
+  x.e = (ag && k < a.K) ? gc * (unsigned)a.K + (unsigned)k : 0u;
+  const float4* Sb = a.S + (size_t)b * (size_t)a.s_env * REC<D>;
+  const float* ab = a.a + (size_t)b * a.N * D;
+  const unsigned j = (unsigned)min(max(a.idx[x.e], 0), a.Nn - 1);
+  x.agent_j = j < (unsigned)a.N;
+  const unsigned ja = x.agent_j ? j : (unsigned)(a.N - 1);
+  load_rec<D>(Sb, i, x.pi, x.vi);
+  load_rec<D>(Sb, j, x.pj, x.vj);
+#pragma unroll
+  for (int q = 0; q < D; ++q) {
+    x.ai[q] = ab[(size_t)i * D + q];
+    x.aj[q] = ab[(size_t)ja * D + q];
+  }
+  x.hv = a.h[x.e];
+  x.i = (int)i;
+  x.j = (int)j;
+}
+
+template <int NW, int D>
+__global__ __launch_bounds__(NW * 64, 1) void refine_local_kernel(RefineSmallArgs sa) {
+  const RefineArgs& a = sa.r;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const RefW w = refine_weights(smem, a);
+  __syncthreads();
+  const int wave = wave_id(), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const unsigned BN = (unsigned)a.B * a.N;
+  const unsigned ntiles = (BN + 1u) / 2u;
+  const unsigned stride = gridDim.x * NW;
+  const int loops = sa.loops;
+  const float dt = a.dt;
+  unsigned tile = (unsigned)blockIdx.x * NW + wave;
+  LocIn<D> nx;
+  refine_local_load<D>(a, tile, r, BN, nx);
+  for (; tile < ntiles; tile += stride) {
+    const LocIn<D> x = nx;
+    refine_local_load<D>(a, tile + stride, r, BN, nx);   // the next tile's gathers (clamped past the end)
+    if (__ballot(x.in) == 0ull) continue;                // every env of the tile masked out (scalar)
+    RefIn<D> cur;
+    cur.in = x.in;
+    cur.i = x.i;
+    cur.j = x.j;
+    cur.hv = x.hv;
+    const bool self = x.j == x.i;
+    float vjn[D], d[D];
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+      const float uj = x.agent_j ? x.aj[q] : 0.f;        // the neighbour's nominal action
+      const float pin = x.pi[q] + x.vi[q] * dt, pjn = x.pj[q] + x.vj[q] * dt;
+      vjn[q] = x.vj[q] + uj * dt;
+      cur.rp[q] = x.in ? pin - pjn : 0.f;
+      d[q] = 0.f;
+    }
+    for (int it = 0; it < loops; ++it) {
+#pragma unroll
+      for (int q = 0; q < D; ++q) {
+        const float ui = x.ai[q] + d[q];
+        const float vin = x.vi[q] + ui * dt;
+        cur.rv[q] = x.in ? vin - (self ? vin : vjn[q]) : 0.f;
+      }
+      RefOut<D> o;
+      refine_tile<D>(cur, w, a, lane, h, o);
+      const bool rec = x.in && h == 0;
+      if (rec && it == 0) {
+        if (a.hn_out) a.hn_out[x.e] = o.hnv;
+        if (a.flag_out) a.flag_out[x.e] = o.on ? 1 : 0;
+      }
+      const unsigned long long act = __ballot(rec && o.on);
+      const unsigned long long s = wave_sum_u64(rec ? refine_viol_fx(o.deriv) : 0ull);
+      if (lane == 0) {
+        if (act) atomicAdd(a.ctl + 2 * it, (unsigned long long)__popcll(act));
+        if (s) atomicAdd(a.ctl + 2 * it + 1, s);
+      }
+      if (act == 0ull) {                                 // scalar: the tile's iterate never changes again
+        if (s)
+          for (int y = it + 1 + lane; y < loops; y += 64) atomicAdd(a.ctl + 2 * y + 1, s);
+        break;
+      }
+      const bool wr = o.on && !self;
+#pragma unroll
+      for (int q = 0; q < D; ++q) {
+        // gv is the h = 0 lane's (refine_tile: the h = 1 lane holds the position rows there); both
+        // halves must step alike, they build the next iteration's fragment together
+        const float gh = wr ? o.gv[q] : 0.f, go = shfl_xor32(gh);
+        float g = 0.f;
+        g += h ? go : gh;
+        g = grp_sum(g);
+        d[q] = refine_step(d[q], a.lr, dt, g);
+      }
+      if (a.a_max > 0.f) {                               // scalar: a kernel argument
+#pragma unroll
+        for (int q = 0; q < D; ++q) d[q] = refine_project(d[q], x.ai[q], a.a_max);
+      }
+    }
+    if (x.live && lane < 32 && (lane & 15) == 0) {
+#pragma unroll
+      for (int q = 0; q < D; ++q) a.delta[(size_t)x.g * D + q] = d[q];
+    }
+  }
+}
+
 }  // namespace MB_PREC
 }  // namespace mb
 
@@ -468,8 +649,11 @@ extern "C" int MB_SYM(refine_prepare)(int dim) {
   using namespace mb::MB_PREC;
   if (dim != 2 && dim != 3) return -1;
   return by_dim(dim, [](auto D) {
-    return (int)hipFuncSetAttribute((const void*)refine_grad_kernel<REFINE_NW, D()>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)REFINE_LDS);
+    const int e = (int)hipFuncSetAttribute((const void*)refine_grad_kernel<REFINE_NW, D()>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)REFINE_LDS);
+    if (e) return e;
+    return (int)hipFuncSetAttribute((const void*)refine_grad_local_kernel<REFINE_NW, D()>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)REFINE_LDS);
   });
 }
 
@@ -481,7 +665,29 @@ extern "C" int MB_SYM(refine_grad)(const mb::RefineArgs* a, int num_blocks, hipS
   if ((long)a->B * a->N * a->K >= (1l << 31) - 32l * 65536) return -3;     // 32-bit edge indexing
   if (a->dim != 2 && a->dim != 3) return -1;
   return by_dim(a->dim, [&](auto D) {     // (the LDS attribute: refine_prepare, once per loop)
+    if (a->local)
+      return launch(refine_grad_local_kernel<REFINE_NW, D()>, dim3(num_blocks), dim3(REFINE_NW * 64), REFINE_LDS, st, *a);
     return launch(refine_grad_kernel<REFINE_NW, D()>, dim3(num_blocks), dim3(REFINE_NW * 64), REFINE_LDS, st, *a);
+  });
+}
+
+// The decentralised filter in one launch (refine_local_kernel): sa->r.ctl (2 * loops words) must be
+// zero at the launch; r.dEv, r.ptr, r.edges and r.it are not used. Sets the kernel's dynamic-LDS
+// attribute itself.
+extern "C" int MB_SYM(refine_local)(const mb::RefineSmallArgs* sa, int num_blocks, hipStream_t st) {
+  using namespace mb;
+  using namespace mb::MB_PREC;
+  const RefineArgs* a = &sa->r;
+  if (a->K > 16 || a->K < 1 || a->B < 1 || a->N < 1 || a->Nn < a->N || num_blocks < 1 || sa->loops < 1) return -1;
+  if (!a->S || !a->idx || !a->a || !a->delta || !a->h || !a->wpack || !a->wrm || !a->wvec || !a->ctl) return -2;
+  if ((long)a->B * a->N * 16 >= (1l << 31) - 32l * 65536) return -3;       // 32-bit indexing of the padded rows
+  if (a->s_env < a->Nn) return -1;
+  if (a->dim != 2 && a->dim != 3) return -1;
+  return by_dim(a->dim, [&](auto D) {
+    const auto kern = refine_local_kernel<REFINE_NW, D()>;
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)REFINE_LDS);
+    if (e != hipSuccess) return (int)e;     // this launcher reports the attribute's error
+    return launch(kern, dim3(num_blocks), dim3(REFINE_NW * 64), REFINE_LDS, st, *sa);
   });
 }
 
@@ -533,15 +739,43 @@ __global__ __launch_bounds__(256) void refine_update_kernel(RefineArgs a) {
   }
 }
 
+// The decentralised filter's loop path (a.local): the agent's own K slots alone, no reverse CSR. A kernel
+// of its own name -- the joint kernel keeps its own, instruction for instruction.
+template <int D>
+__global__ __launch_bounds__(256) void refine_update_local_kernel(RefineArgs a) {
+  if (a.ctl[2 * a.it] == 0ull) return;                     // no active edge: dEv is all zeros
+  const long node = ((long)blockIdx.x * blockDim.x + threadIdx.x) / RG;
+  if (node >= (long)a.B * a.N) return;                     // whole 16-lane groups
+  const int l = threadIdx.x % RG;
+  const int N = a.N, K = a.K, NK = N * K;
+  const int b = (int)(node / N), i = (int)(node % N);
+  if (a.env_active && a.env_active[b] == 0) return;        // masked-out env: delta stays zero (whole group)
+  float g[D];
+  MB_PREC::refine_node_grad<D, true>(a.dEv + (size_t)b * NK * D, nullptr, nullptr, i, l, K, NK, g);
+  if (l != 0) return;
+  float* d = a.delta + ((size_t)b * N + i) * D;
+#pragma unroll
+  for (int q = 0; q < D; ++q) d[q] = MB_PREC::refine_step(d[q], a.lr, a.dt, g[q]);
+  if (a.a_max > 0.f) {                                     // scalar: a kernel argument
+    const float* ac = a.a + ((size_t)b * N + i) * D;
+#pragma unroll
+    for (int q = 0; q < D; ++q) d[q] = MB_PREC::refine_project(d[q], ac[q], a.a_max);
+  }
+}
+
 }  // namespace mb
 
 extern "C" int mb_refine_update(const mb::RefineArgs* a, hipStream_t st) {
   using namespace mb;
   if (a->K > 16 || a->K < 1 || a->B < 1 || a->N < 1 || a->Nn < a->N || a->it < 0) return -1;
-  if (!a->delta || !a->dEv || !a->ptr || !a->edges || !a->ctl || (a->a_max > 0.f && !a->a)) return -2;
+  if (!a->delta || !a->dEv || !a->ctl || (a->a_max > 0.f && !a->a)) return -2;
+  if (!a->local && (!a->ptr || !a->edges)) return -2;      // the joint update walks the reverse CSR
   const long total = (long)a->B * a->N * RG;
   const dim3 grid((unsigned)((total + 255) / 256));
   if (a->dim != 2 && a->dim != 3) return -1;
-  return by_dim(a->dim, [&](auto D) { return launch(refine_update_kernel<D()>, grid, dim3(256), 0, st, *a); });
+  return by_dim(a->dim, [&](auto D) {
+    if (a->local) return launch(refine_update_local_kernel<D()>, grid, dim3(256), 0, st, *a);
+    return launch(refine_update_kernel<D()>, grid, dim3(256), 0, st, *a);
+  });
 }
 #endif

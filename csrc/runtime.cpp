@@ -463,6 +463,7 @@ class BpttDriver {
 struct RefineCall {
   mb::RefineSmallArgs sa;       // sa.r: both filters; sa.ew: the persistent filter's result words
   int num_blocks, prec;         // num_blocks: refine_grad's grid (the loop filter's alone, as r.dEv and r.ctl)
+  int fused, fused_blocks;      // decentralised filter (r.local): one refine_local launch of fused_blocks workgroups
 };
 
 RefineCall refine_call(Args& x) {
@@ -476,6 +477,8 @@ RefineCall refine_call(Args& x) {
   x("flag_out", r.flag_out); x("env_active", r.env_active); x("loops", c.sa.loops); x.opt("ew", c.sa.ew);
   x.opt("num_blocks", c.num_blocks); x("prec", c.prec);
   x.opt("a_max", r.a_max);                // the actuator limit: off (0) without the key
+  x.opt("local", r.local);                // the decentralised filter: the joint one (0) without the key
+  x.opt("fused", c.fused); x.opt("fused_blocks", c.fused_blocks);
   return c;
 }
 
@@ -490,8 +493,8 @@ int refine_loop(const RefineCall* c, hipStream_t st) {
   if ((r.dim != 2 && r.dim != 3) || r.B < 1 || r.N < 1 || r.Nn < r.N || r.K < 1 || r.K > 16 || loops < 0 ||
       c->num_blocks < 1 || r.f_bwd < 0 || r.s_env < r.Nn || c->prec < 0 || c->prec > 2 || !(r.a_max >= 0.f))
     return -1;
-  if (!r.S || !r.idx || !r.a || !r.delta || !r.h || !r.wpack || !r.wrm || !r.wvec || !r.dEv || !r.ptr || !r.edges || !r.ctl)
-    return -2;
+  if (!r.S || !r.idx || !r.a || !r.delta || !r.h || !r.wpack || !r.wrm || !r.wvec || !r.dEv || !r.ctl) return -2;
+  if (!r.local && (!r.ptr || !r.edges)) return -2;             // the joint update walks the reverse CSR
   if (loops == 0) return 0;
   const hipError_t e = hipMemsetAsync(r.ctl, 0, (size_t)loops * 2 * sizeof(unsigned long long), st);
   if (e != hipSuccess) return (int)e;
@@ -525,6 +528,23 @@ int refine_small(const RefineCall* c, hipStream_t st) {
   return by_prec(c->prec, mb_refine_small, mb_refine_small_f16, mb_refine_small_x3)(&c->sa, st);
 }
 
+// Decentralised safety filter (csrc/refine.hip refine_local_kernel): the whole loop of every agent in
+// ONE launch on the caller's stream. The pointers and sizes are validated once; the control words (2
+// per iteration, the loop path's array) are cleared here; delta arrives zeroed; no reverse CSR, no
+// dEv; no host synchronisation. The kernel writes r.hn_out / r.flag_out at iteration 0 only.
+int refine_local(const RefineCall* c, hipStream_t st) {
+  const mb::RefineArgs& r = c->sa.r;
+  const int loops = c->sa.loops;
+  if ((r.dim != 2 && r.dim != 3) || r.B < 1 || r.N < 1 || r.Nn < r.N || r.K < 1 || r.K > 16 || loops < 0 ||
+      c->fused_blocks < 1 || r.f_bwd < 0 || r.s_env < r.Nn || c->prec < 0 || c->prec > 2 || !(r.a_max >= 0.f) || !r.local)
+    return -1;
+  if (!r.S || !r.idx || !r.a || !r.delta || !r.h || !r.wpack || !r.wrm || !r.wvec || !r.ctl) return -2;
+  if (loops == 0) return 0;
+  const hipError_t e = hipMemsetAsync(r.ctl, 0, (size_t)loops * 2 * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return (int)e;
+  return by_prec(c->prec, mb_refine_local, mb_refine_local_f16, mb_refine_local_x3)(&c->sa, c->fused_blocks, st);
+}
+
 // The arguments of the three launches of csrc/episode.hip (the driver sets S_cur / S_next per step)
 mb::EpisodeArgs episode_args(Args& x) {
   mb::EpisodeArgs e{};
@@ -542,7 +562,8 @@ mb::EpisodeArgs episode_args(Args& x) {
 // training, evaluation -- with or without the safety filter, as one call. Per step, on the caller's
 // stream: cell_sort + ONE scan of s_t (kNN and the safety count of the step before), the controller
 // forward, with an actuator limit episode_limit, the filter (cbf_fwd for h(s_t), rev_csr, refine_loop
-// or refine_small), episode_advance,
+// or refine_small; the decentralised filter: cbf_fwd, then refine_local -- the ctl memset and one
+// launch -- or its loop path, and no rev_csr), episode_advance,
 // episode_tally, and a swap of the two record buffers. The buffers come from Python
 // (ops/episode.py), validated there once per call; nothing is allocated and the host does not wait
 // inside a step. Every check_every steps the "some env still runs" word is copied to pinned memory
@@ -604,9 +625,10 @@ class EpisodeDriver {
     const mb::ScanArgs &s = g.scan, &f = g.scan_final;
     const mb::CtrlArgs& a = g.ctrl;
     const bool filter = e.mode != 0;
+    const bool local = filter && g.r.sa.r.local != 0;         // the decentralised filter needs no reverse CSR
     if (e.B < 1 || e.N < 1 || s.Nn < e.N || e.s_env != s.Nn || s.K < 1 || s.K > 16 || s.K > s.Nn || (e.dim != 2 && e.dim != 3) ||
         g.max_steps < 0 || e.loops < 0 || e.mode < 0 || e.mode > 2 || g.prec_ctrl < 0 || g.prec_ctrl > 2 || filter == none ||
-        no_cbf != none || no_csr != none || s.B != e.B || s.N != e.N || s.dim != e.dim || s.s_env != s.Nn || f.B != e.B ||
+        no_cbf != none || (local ? !no_csr : no_csr != none) || s.B != e.B || s.N != e.N || s.dim != e.dim || s.s_env != s.Nn || f.B != e.B ||
         f.N != e.N || f.Nn != s.Nn || f.dim != e.dim || f.s_env != s.Nn || a.B != e.B || a.N != e.N || a.K != s.K ||
         a.dim != e.dim || a.s_env != s.Nn || g.sort.B != e.B || g.sort.N != s.Nn || g.sort.s_env != s.Nn)
       throw std::invalid_argument("EpisodeDriver: bad dimensions");
@@ -623,12 +645,15 @@ class EpisodeDriver {
       if (r.B != e.B || r.N != e.N || r.Nn != s.Nn || r.K != s.K || r.dim != e.dim || e.loops < 1 ||
           g.r.sa.loops != e.loops || g.r.sa.ew != e.ew || g.r.prec < 0 || g.r.prec > 2 || r.idx != s.idx ||
           g.cbf.B != e.B || g.cbf.T != 1 || g.cbf.N != e.N || g.cbf.K != s.K || g.cbf.dim != e.dim || g.cbf.idx != s.idx ||
-          g.csr.G != e.B || g.csr.N != e.N || g.csr.K != s.K || g.csr.Nn != s.Nn || g.csr.idx != s.idx)
+          (!local && (g.csr.G != e.B || g.csr.N != e.N || g.csr.K != s.K || g.csr.Nn != s.Nn || g.csr.idx != s.idx)) ||
+          (local && e.mode != 1) || (g.r.fused && !local))
         throw std::invalid_argument("EpisodeDriver: bad dimensions");
-      if (!r.wpack || !r.wrm || !r.wvec || !r.delta || r.delta != e.delta || !r.h || g.cbf.h_out != r.h || !r.ptr ||
-          g.csr.ptr != r.ptr || !r.edges || g.csr.edges != r.edges || !g.cbf.wpack || !g.cbf.wvec || g.cbf_blocks < 1)
+      if (!r.wpack || !r.wrm || !r.wvec || !r.delta || r.delta != e.delta || !r.h || g.cbf.h_out != r.h ||
+          (!local && (!r.ptr || g.csr.ptr != r.ptr || !r.edges || g.csr.edges != r.edges)) || !g.cbf.wpack || !g.cbf.wvec ||
+          g.cbf_blocks < 1)
         throw std::invalid_argument("EpisodeDriver: a filter buffer is missing");
-      if (e.mode == 2 ? (!e.ew || s.Nn > 64) : (!r.dEv || !r.ctl || g.r.num_blocks < 1))
+      if (e.mode == 2 ? (!e.ew || s.Nn > 64)
+                      : (!r.ctl || (g.r.fused ? g.r.fused_blocks < 1 : (!r.dEv || g.r.num_blocks < 1))))
         throw std::invalid_argument("EpisodeDriver: the filter's result words / workspace are missing");
     }
     return g;
@@ -677,9 +702,10 @@ class EpisodeDriver {
     mb::CbfFwdArgs a = g.cbf;
     r.S = a.S = S;         // the step's h(s_t) and reverse CSR are written where the filter reads them
     chk(by_prec(c.prec, mb_cbf_fwd, mb_cbf_fwd_f16, mb_cbf_fwd_x3)(&a, g.cbf_blocks, st), "cbf_fwd");
-    chk(mb_rev_csr(&g.csr, st), "rev_csr");
+    if (!r.local) chk(mb_rev_csr(&g.csr, st), "rev_csr");
     if (!g.mask_done) r.env_active = nullptr;        // validate.py's rule: a finished env is not refined
-    if (g.e.mode == 2) chk(refine_small(&c, st), "refine_small");
+    if (c.fused) chk(refine_local(&c, st), "refine_local");
+    else if (g.e.mode == 2) chk(refine_small(&c, st), "refine_small");
     else chk(refine_loop(&c, st), "refine_loop");
   }
 
@@ -691,6 +717,7 @@ class EpisodeDriver {
 void register_runtime(py::module& m) {
   def_launch(m, "refine_loop", refine_call, refine_loop);
   def_launch(m, "refine_small", refine_call, refine_small);
+  def_launch(m, "refine_local", refine_call, refine_local);
   // the three launches of csrc/episode.hip on their own, as EpisodeDriver issues them per step
   def_launch(m, "episode_limit", episode_args, mb_episode_limit);
   def_launch(m, "episode_advance", episode_args, mb_episode_advance);

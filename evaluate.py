@@ -4,7 +4,8 @@
                        [--max_steps 50] [--no_refine] [--refine_space actions|gains] [--diagnose]
                        [--dim 2|3] [--num_obstacles M] [--dtype fp32|bf16|fp16]
                        [--refine_impl autograd|native] [--rollout_impl python|native]
-                       [--a_max A] [--action_stats] [--device auto|cpu|hip] [--gpu 0]
+                       [--a_max A] [--action_stats] [--refine_coupling joint|local]
+                       [--device auto|cpu|hip] [--gpu 0]
 
 Prints one JSON line: safety rate, reaching rate, mean final goal distance, refinement
 iterations. Without --model_path the networks are random-initialised (plumbing check).
@@ -18,6 +19,8 @@ or --refine_impl native, not with --diagnose or --refine_space gains).
 --a_max A limits every component of the applied action to [-A, A] (the nominal action is clamped,
 the filter projects onto the box; not with --diagnose or --refine_space gains) and, like
 --action_stats alone, adds limited_rate, intervention_rate, mean_abs_delta and max_abs_action.
+--refine_coupling local runs the decentralised filter: every agent refines its own action against its
+neighbours' nominal next states (not with --refine_space gains).
 """
 from __future__ import annotations
 
@@ -50,6 +53,8 @@ def main(argv=None):
                     help="per-axis actuator limit |u| <= A on the applied action (default: none)")
     ap.add_argument("--action_stats", action="store_true",
                     help="report limited_rate, intervention_rate, mean_abs_delta and max_abs_action")
+    ap.add_argument("--refine_coupling", choices=["joint", "local"], default="joint",
+                    help="joint: the centralised filter; local: every agent refines its own action alone")
     args = ap.parse_args(argv)
     if args.gpu is not None:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)
@@ -76,7 +81,8 @@ def main(argv=None):
     cfg = EvalConfig(num_agents=args.num_agents, num_envs=args.num_envs, seed=args.seed, refine=not args.no_refine,
                      refine_space=args.refine_space, diagnose=args.diagnose, dim=args.dim,
                      num_obstacles=args.num_obstacles, dtype=args.dtype, refine_impl=args.refine_impl,
-                     rollout_impl=args.rollout_impl, a_max=args.a_max, action_stats=args.action_stats)
+                     rollout_impl=args.rollout_impl, a_max=args.a_max, action_stats=args.action_stats,
+                     refine_coupling=args.refine_coupling)
     if args.episodes is not None:
         cfg.episodes = args.episodes
     if args.max_steps is not None:
@@ -88,7 +94,8 @@ def main(argv=None):
     try:
         out = evaluate(ctrl, cbf, cfg, device=dev)
     except ValueError as e:
-        if not ((cfg.rollout_impl == "native" and "rollout_impl" in str(e)) or (cfg.a_max is not None and "a_max" in str(e))):
+        if not ((cfg.rollout_impl == "native" and "rollout_impl" in str(e)) or (cfg.a_max is not None and "a_max" in str(e)) or
+                (cfg.refine_coupling != "joint" and "refine_coupling" in str(e))):
             raise
         ap.error(str(e))
     out.update({"num_agents": args.num_agents, "num_envs": args.num_envs, "episodes": cfg.episodes,
@@ -98,6 +105,8 @@ def main(argv=None):
         out["rollout_impl"] = cfg.rollout_impl
     if cfg.a_max is not None:
         out["a_max"] = cfg.a_max
+    if cfg.refine_coupling != "joint":
+        out["refine_coupling"] = cfg.refine_coupling
     print(json.dumps(out), flush=True)
     return out
 

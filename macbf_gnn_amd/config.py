@@ -110,6 +110,7 @@ class TrainConfig:
                                       # native call per rollout (ops/episode.py), the same integer totals
     val_a_max: float = 0.0            # per-axis actuator limit |u| <= val_a_max on both validation rollouts
                                       # (evaluate.py, "Actuator limit"); 0: off. The training rollouts' limit is a_max
+    val_refine_coupling: str = "joint"  # the validation filter: "joint" | "local" (evaluate.py, "Coupling"), both val_impls
     save_best: bool = False           # keep <model_path>.best (+ .best.json) at the best validation so far
     best_metric: str = ""             # a val_*_rate key, higher is better; "": val_refined_safety_rate
                                       # (val_safety_rate with val_refine off)

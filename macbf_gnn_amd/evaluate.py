@@ -34,6 +34,22 @@ and native paths agree bit for bit.
 The early-out rule does not change: an iteration without an active edge ends the work, and a
 saturated agent can keep an edge active for all ``loops`` iterations.
 
+Coupling (``refine_coupling``, opt-in). ``"joint"`` (the default) is the filter above: one optimisation
+over the whole scene, s'_j is formed from a_j + delta_j, so agent i's barrier also pushes its
+neighbours' actions and every iteration is a round of neighbour-to-neighbour communication.
+``"local"`` is the decentralised filter: every agent refines its own action alone.
+    own state    s'_i = s_i + dt [v_i, a_i + delta_i]
+    neighbours   s'_j = s_j + dt [v_j, a_j] for every slot with j != i: the neighbour's NOMINAL next state
+                 (with a limit a_j is the clamped a_c; an obstacle node has a zero action)
+    self slot    (idx == i) the agent's own refined state: its relative state is exactly zero and it
+                 carries no gradient, as in the joint filter
+    update       delta_i <- delta_i - lr * dt * sum_k dEv[i, k] over the agent's own K slots; no in-edge term
+The hinge, the radius mask at s', h(s_t), the expression order of deriv, the projection onto the actuator
+box and the final clamp are the joint filter's, and so are the result words: ``counts[it]`` the edges with
+a non-zero hinge gradient in iteration it, ``viol`` the hinge sum over all edges at the last evaluated
+iterate. An agent whose K edges are all inactive never moves again (its neighbours' terms are fixed), so
+the stop rule -- an iteration that counts no active edge ends the work -- stays exact.
+
 Action statistics (``ACTION_STATS``, with ``action_stats`` or a limit), over the agents of the envs
 that are active at the start of a step (the mask that weights ``agent_steps``): agents with some
 |u_q| == a_max, agents with some delta_q != 0, the sum over agents and components of
@@ -81,6 +97,9 @@ class EvalConfig:
     a_max: Optional[float] = None   # per-axis actuator limit on the applied action (module docstring); None: off.
                                     # Not with refine_space="gains" or diagnose. Implies action_stats
     action_stats: bool = False      # add limited_rate, intervention_rate, mean_abs_delta, max_abs_action
+    refine_coupling: str = "joint"  # "joint": the centralised filter | "local": every agent refines its own action
+                                    # against its neighbours' nominal next states (module docstring). Not with
+                                    # refine_space="gains"
 
 
 MFMA_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
@@ -101,6 +120,24 @@ def check_a_max(a_max) -> Optional[float]:
     if not math.isfinite(m) or m <= 0.0:
         raise ValueError(f"a_max = {a_max!r} is not a positive finite fp32 number")
     return m
+
+
+COUPLINGS = ("joint", "local")
+
+
+def check_coupling(coupling) -> str:
+    if coupling not in COUPLINGS:
+        raise ValueError(f"unknown coupling {coupling!r} (joint or local)")
+    return coupling
+
+
+def check_refine_coupling(cfg: "EvalConfig") -> str:
+    """``cfg.refine_coupling`` checked; the option it cannot be combined with is an error that names it."""
+    c = check_coupling(cfg.refine_coupling)
+    if c == "local" and cfg.refine and cfg.refine_space == "gains":
+        raise ValueError("refine_coupling='local' refines free actions: refine_space='gains' has no local variant; use "
+                         "refine_space='actions' or refine_coupling='joint'")
+    return c
 
 
 def check_action_limit(cfg: "EvalConfig") -> Optional[float]:
@@ -170,9 +207,17 @@ def _euler(s, a):
 
 
 def refine_actions(cbf, s, a, idx, loops: int = C.REFINE_LOOPS, lr: float = C.REFINE_LEARNING_RATE,
-                   check_every: int = 10, obstacles=None, a_max=None, return_delta: bool = False):
+                   check_every: int = 10, obstacles=None, a_max=None, return_delta: bool = False,
+                   coupling: str = "joint"):
     """Gradient refinement of the actions on the discrete CBF condition. Returns
     (refined actions, iterations used, remaining violation sum).
+
+    ``coupling``: "joint" (the loop below, through ``cbf``) or "local" (the decentralised rule of the
+    module docstring). The local filter is built from the oracle's functions -- ``oracle.edge_rel`` of
+    the refined states against the nominal next nodes, the self rows zeroed, then the layers of
+    ``oracle.cbf_forward`` on ``cbf.params_dict()`` -- in fp32 torch ops on whatever device the tensors
+    are on. It does not go through the native autograd Functions: on a HIP device it is the slow
+    reference of ``ops.refine.safety_filter(coupling="local")``, not a production path.
 
     ``a_max``: the actuator limit of the module docstring -- the action is clamped first, every step is
     projected onto [lo, hi] and the result is clamp(a_c + delta). ``return_delta`` appends ``delta``.
@@ -185,18 +230,24 @@ def refine_actions(cbf, s, a, idx, loops: int = C.REFINE_LOOPS, lr: float = C.RE
     ``obstacles`` (B, M, D): static points among the neighbour slots of ``idx``; they have no action
     and do not move, so ``delta`` stays (B, N, D)."""
     a_max = check_a_max(a_max)
+    local = check_coupling(coupling) == "local"
     with torch.no_grad():
-        h = cbf(s, idx=idx, obstacles=obstacles)
         if a_max is not None:
             a = a.clamp(-a_max, a_max)
             lo, hi = -a_max - a, a_max - a
+        if local:
+            p = {k: v.detach() for k, v in cbf.params_dict().items()}
+            h = oracle.cbf_forward(p, s, idx, nodes=oracle.with_obstacles(s, obstacles))
+            nominal = oracle.with_obstacles(_euler(s, a), obstacles)      # s'_j of every node, fixed over the loop
+        else:
+            h = cbf(s, idx=idx, obstacles=obstacles)
     delta = torch.zeros_like(a, requires_grad=True)
     viol = torch.zeros((), device=s.device)
     used = torch.zeros((), dtype=torch.int64, device=s.device)
     for it in range(1, loops + 1):
         ar = a + delta
         s_next = _euler(s, ar)
-        hn = cbf(s_next, idx=idx, obstacles=obstacles)
+        hn = _cbf_local(p, s_next, idx, nominal) if local else cbf(s_next, idx=idx, obstacles=obstacles)
         deriv = hn - h + C.TIME_STEP * C.ALPHA_CBF * h
         viol = torch.relu(-deriv).sum()
         pending = viol.detach() > 0
@@ -214,6 +265,22 @@ def refine_actions(cbf, s, a, idx, loops: int = C.REFINE_LOOPS, lr: float = C.RE
     if return_delta:
         return out, int(used), float(viol.detach()), delta.detach()
     return out, int(used), float(viol.detach())
+
+
+def _cbf_local(p, s_next, idx, nominal):
+    """h(s') of the local coupling: centre rows from ``s_next`` (the refined states), neighbour rows from
+    ``nominal`` (the nominal next nodes), the self slots exactly zero; then ``oracle.cbf_forward``'s layers."""
+    D = s_next.shape[-1] // 2
+    rel, eye = oracle.edge_rel(s_next, idx, nodes=nominal)
+    rel = torch.where(eye.bool().unsqueeze(-1), torch.zeros_like(rel), rel)
+    d = torch.sqrt(oracle.sq_dist(rel, D) + C.CBF_DIST_EPS_COORD * D)
+    z = torch.cat([rel, eye.unsqueeze(-1), (d - C.DIST_MIN_THRES).unsqueeze(-1)], dim=-1)
+    mask = (d <= C.OBS_RADIUS).to(s_next.dtype)
+    for i, act in ((0, True), (2, True), (4, True), (6, False)):
+        z = oracle._lin(z, p[f"cbf_net.{i}.weight"], p[f"cbf_net.{i}.bias"], first=i == 0, head=i == 6)
+        if act:
+            z = torch.relu(z)
+    return z[..., 0] * mask
 
 
 def _pd_action(s, g, y):
@@ -297,7 +364,8 @@ def _rollout_native(controller, cbf, s0, g, cfg: EvalConfig, obstacles) -> Dict[
     stats = cfg.action_stats or a_max is not None
     vec = episode.run_episodes(controller, cbf, s0, g, obstacles, refine=cfg.refine, loops=cfg.refine_loops,
                                lr=cfg.refine_lr, max_steps=cfg.max_steps, top_k=cfg.top_k, mask_done=False,
-                               check_every=V.CHECK_EVERY, a_max=a_max, action_stats=stats)
+                               check_every=V.CHECK_EVERY, a_max=a_max, action_stats=stats,
+                               coupling=check_refine_coupling(cfg))
     if stats:
         vec = torch.cat(vec)
     tot = [int(x) for x in vec.tolist()]                             # the one host read
@@ -321,6 +389,7 @@ def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dic
         raise ValueError(f"unknown refine_impl {cfg.refine_impl!r} (autograd or native)")
     check_rollout_impl(cfg, s0.device)
     a_max = check_action_limit(cfg)
+    coupling = check_refine_coupling(cfg)
     stats = cfg.action_stats or a_max is not None
     if cfg.rollout_impl == "native":
         return _rollout_native(controller, cbf, s0, g, cfg, obstacles)
@@ -358,11 +427,12 @@ def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dic
         elif native_filter:
             from .ops import refine as refine_ops
             a, used, _, delta = refine_ops.safety_filter(cbf, s, a, idx, obstacles=obs, loops=cfg.refine_loops,
-                                                         lr=cfg.refine_lr, a_max=a_max, return_delta=True)
+                                                         lr=cfg.refine_lr, a_max=a_max, return_delta=True,
+                                                         coupling=coupling)
             iters_dev += used
         elif cfg.refine:
             a, it, _, delta = refine_actions(cbf, s, a, idx, cfg.refine_loops, cfg.refine_lr, obstacles=obs, a_max=a_max,
-                                             return_delta=True)
+                                             return_delta=True, coupling=coupling)
             refine_iters += it
         with torch.no_grad():
             if stats:
@@ -427,6 +497,7 @@ def evaluate(controller, cbf, cfg: EvalConfig, device: Optional[torch.device] = 
         raise ValueError(f"dtype must be one of {sorted(MFMA_DTYPES)}, got {cfg.dtype!r}")
     check_rollout_impl(cfg, device)
     check_action_limit(cfg)
+    check_refine_coupling(cfg)
     if device.type == "cuda":
         controller.mfma_dtype = cbf.mfma_dtype = MFMA_DTYPES[cfg.dtype]
     controller.eval()

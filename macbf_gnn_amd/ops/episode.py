@@ -5,7 +5,9 @@ torch ops, as one native call.
 Per step the driver enqueues, on the current stream: one scan of s_t (the kNN lists and, from the
 same launch, the safety count that belongs to the step before), the controller forward, with
 ``refine`` the safety filter (``cbf_fwd`` for h(s_t), ``rev_csr``, then the loop or the persistent
-filter, as ``ops.refine.choose_impl`` picks), the Euler step and the step's bookkeeping. Both
+filter, as ``ops.refine.choose_impl`` picks; with ``coupling="local"``, the decentralised filter of
+``evaluate.py``'s module docstring: ``cbf_fwd``, the control words' memset and one ``refine_local``
+launch -- no ``rev_csr``, no loop of launches), the Euler step and the step's bookkeeping. Both
 networks are packed once per call. The host reads the "some env still runs" word every
 ``check_every`` steps and nothing else; a step issued after every env finished changes neither the
 states nor a count, so the result does not depend on that period.
@@ -39,11 +41,12 @@ from .refine import choose_impl
 
 def run_episodes(controller, cbf, s0, g, obstacles=None, *, refine, loops=C.REFINE_LOOPS,
                  lr=C.REFINE_LEARNING_RATE, max_steps=C.INNER_LOOPS, top_k=C.TOP_K, mask_done=True, check_every=5,
-                 impl=None, return_state=False, a_max=None, action_stats=False):
+                 impl=None, return_state=False, a_max=None, action_stats=False, coupling="joint"):
     """s0 (B, N, 2D), g (B, N, D) on the HIP device, obstacles (B, M, D) or None -> the batch's totals,
     an int64 device vector in the order of ``validate.COUNTS``; with ``return_state`` also the final
     states (B, N, 2D) and the final ``active`` (B,) bool. ``impl``: the filter's implementation
-    (None / "loop" / "persistent", ``ops.refine``). Nothing is read on the host except the driver's
+    (None / "loop" / "persistent", ``ops.refine``); ``coupling`` "joint" / "local" (with "local" ``impl`` is
+    None / "fused" / "loop"). Nothing is read on the host except the driver's
     flag; the caller decides when to read the vector. ``a_max``: the actuator limit (module docstring);
     ``action_stats=True`` appends one more element to the result, the int64 device vector of
     ``evaluate.ACTION_STATS``."""
@@ -57,6 +60,8 @@ def run_episodes(controller, cbf, s0, g, obstacles=None, *, refine, loops=C.REFI
     if K > C.MAX_TOP_K:
         raise native.NativeError(f"K = {K} neighbour slots, the kernels take at most MAX_TOP_K = {C.MAX_TOP_K}")
     loops, max_steps = int(loops), int(max_steps)
+    if refine:
+        choose_impl(impl, "fp32", 1, 1, coupling)       # an unknown coupling / impl pair: refused before any work
     if a_max is not None:                       # the fp32 value the kernels compare with
         a_max = float(torch.tensor(native._a_max(a_max), dtype=torch.float32))
     dev = s0.device
@@ -85,7 +90,8 @@ def run_episodes(controller, cbf, s0, g, obstacles=None, *, refine, loops=C.REFI
             S0 = S0.clone()                                             # never write into the caller's states
         Nn = S0.shape[1]
         filt = bool(refine) and loops > 0
-        persistent = filt and choose_impl(impl, bmp.prec, Nn, K) == "persistent"
+        which = choose_impl(impl, bmp.prec, Nn, K, coupling, B * N) if filt else None
+        persistent, local, fused = which == "persistent", filt and coupling == "local", which == "fused"
         i64 = dict(dtype=torch.int64, device=dev)
         st = torch.zeros(native.EP_WORDS, **i64)
         st[0] = 1
@@ -102,17 +108,19 @@ def run_episodes(controller, cbf, s0, g, obstacles=None, *, refine, loops=C.REFI
             buf.update(act_st=torch.zeros(native.EP_ACT_WORDS, **i64), act_out=torch.empty(native.EP_ACT_WORDS, **i64))
         if filt:
             buf.update(delta=torch.zeros(B, N, D, dtype=torch.float32, device=dev),
-                       h=torch.empty(B, N, K, dtype=torch.float32, device=dev),
-                       rptr=torch.empty(B, Nn + 1, dtype=torch.int32, device=dev),
-                       redges=torch.empty(B, N * K, dtype=torch.int32, device=dev))
+                       h=torch.empty(B, N, K, dtype=torch.float32, device=dev))
+            if not local:
+                buf.update(rptr=torch.empty(B, Nn + 1, dtype=torch.int32, device=dev),
+                           redges=torch.empty(B, N * K, dtype=torch.int32, device=dev))
             if persistent:
                 buf["ew"] = torch.zeros(B, loops, 2, **i64)
             else:
                 buf["ctl"] = torch.zeros(2 * loops, **i64)
-                buf["dEv"] = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
+                if not fused:
+                    buf["dEv"] = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
         _, cur = native.episode_run(buf, K=K, max_steps=max_steps, check_every=check_every, refine=refine, loops=loops,
                                     lr=lr, mask_done=mask_done, persistent=persistent, ctrl=(cw, cv, crm, cmp_),
-                                    cbf=(bw, bv, brm, bmp) if refine else None, a_max=a_max)
+                                    cbf=(bw, bv, brm, bmp) if refine else None, a_max=a_max, local=local, fused=fused)
         res = (buf["out"],)
         if return_state:
             s_fin = native.from_records(buf["S1" if cur else "S0"][:, :N]).to(s0.dtype).contiguous()

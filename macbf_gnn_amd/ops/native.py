@@ -890,9 +890,10 @@ def _a_max(a_max) -> float:
 
 
 def _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec, hn_out, flag_out,
-                 env_active, lr, a_max=None):
-    """The argument validation shared by ``refine`` and ``refine_small`` ->
-    (B, N, Nn, K, D, loops, precision code, the RefineArgs fields of ``_refine_kw``)."""
+                 env_active, lr, a_max=None, local=False):
+    """The argument validation shared by ``refine``, ``refine_small`` and ``refine_local`` ->
+    (B, N, Nn, K, D, loops, precision code, the RefineArgs fields of ``_refine_kw``). ``local``: the
+    decentralised filter, which has no reverse CSR (rptr / redges must be None)."""
     if S is None or S.dim() != 3:
         raise NativeError("S must be (B, Nn, 4|8) node records")
     B, Nn, W = S.shape
@@ -910,11 +911,17 @@ def _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loo
         if t is None:
             raise NativeError(f"{name} is required")
         check(t, torch.float32, (B, N, D), name)
-    if h is None or rptr is None or redges is None:
-        raise NativeError("h, rptr and redges are required")
+    if h is None:
+        raise NativeError("h is required")
     check(h, torch.float32, (B, N, K), "h")
-    check(rptr, torch.int32, (B, Nn + 1), "rptr")
-    check(redges, torch.int32, (B, N * K), "redges")
+    if local:
+        if rptr is not None or redges is not None:
+            raise NativeError("the decentralised filter takes no reverse CSR (rptr / redges)")
+    else:
+        if rptr is None or redges is None:
+            raise NativeError("h, rptr and redges are required")
+        check(rptr, torch.int32, (B, Nn + 1), "rptr")
+        check(redges, torch.int32, (B, N * K), "redges")
     loops = int(loops)
     if loops < 0:
         raise NativeError("loops must be >= 0")
@@ -937,14 +944,16 @@ def _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loo
         check(env_active, env_active.dtype, (B,), "env_active")
         if env_active.dtype == torch.bool:
             env_active = env_active.view(torch.uint8)         # same bytes, 0 / 1
+    extra = dict(local=1) if local else {}
     return B, N, Nn, K, D, loops, code, _refine_kw(B, N, Nn, K, D, S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr,
-                                                   redges, lr, hn_out, flag_out, env_active, a_max=a_max)
+                                                   redges, lr, hn_out, flag_out, env_active, a_max=a_max, **extra)
 
 
 def _refine_kw(B, N, Nn, K, D, S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, lr, hn_out=None,
                flag_out=None, env_active=None, a_max=None, **loop):
     """The RefineArgs fields (csrc/args.h) both filters take; `loop`: what the caller adds (dEv, ctl, launch
-    parameters). The actuator limit is an optional key of the native layer: passed only when one is set."""
+    parameters, local=1 for the decentralised filter). The actuator limit is an optional key of the native
+    layer: passed only when one is set."""
     if _a_max(a_max) > 0.0:
         loop["a_max"] = _a_max(a_max)
     return dict(S=ptr(S), s_env=Nn, dim=D, idx=ptr(idx), a=ptr(a), delta=ptr(delta), h=ptr(h), B=B, N=N, Nn=Nn, K=K,
@@ -955,7 +964,7 @@ def _refine_kw(B, N, Nn, K, D, S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rpt
 
 
 def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl, *, loops, lr,
-           prec=None, hn_out=None, flag_out=None, num_blocks=None, env_active=None, a_max=None):
+           prec=None, hn_out=None, flag_out=None, num_blocks=None, env_active=None, a_max=None, local=False):
     """The safety-filter loop (csrc/refine.hip + the driver in csrc/runtime.cpp): ``loops`` gradient
     steps of ``delta`` (B, N, D), in place, on sum_e relu(-(h(s') - h + dt alpha h)) with
     s' = s + dt [v, a + delta].
@@ -971,11 +980,13 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
     and ctl counts the other envs alone; None is every env. The mask is read by the kernels only.
     a_max (optional): the per-axis actuator limit -- ``a`` must already be clamped to [-a_max, a_max];
     every update then projects delta onto [-a_max - a, a_max - a]. No host synchronisation.
+    local=True: the decentralised filter's loop path (refine_grad_local_kernel, refine_update_local_kernel;
+    ``evaluate.py``'s module docstring) -- rptr and redges must be None.
     fp32 (x3) and bf16 builds; fp16 is not supported (the -1 upstream gradient has no loss scaling)."""
     if dEv is None or ctl is None:
         raise NativeError("dEv and ctl are required")
     B, N, Nn, K, D, loops, code, kw = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, rptr, redges, loops, prec,
-                                                   hn_out, flag_out, env_active, lr, a_max)
+                                                   hn_out, flag_out, env_active, lr, a_max, local=local)
     check(dEv, torch.float32, (B, N, K, D), "dEv")
     check(ctl, torch.int64, None, "ctl")
     if ctl.dim() != 1 or ctl.numel() < 2 * loops:
@@ -988,6 +999,49 @@ def refine(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, dEv, rptr, redges, ctl,
         raise NativeError("num_blocks outside 1..4096")
     _ok(lib().refine_loop(loops=loops, num_blocks=nb, prec=code, stream=stream_handle(), dEv=ptr(dEv), ctl=ptr(ctl), **kw),
         "refine")
+    return nb
+
+
+def refine_local_grid(BN: int, device, prec_code: int) -> int:
+    """Workgroups of refine_local over BN agents: a tile is 2 agents x 16 slots and runs its whole loop in
+    one wave (csrc/refine.hip REFINE_NW waves per workgroup). One workgroup per REFINE_NW tiles, capped at
+    4 * CUs: beyond that a wave walks several tiles (grid stride). The LDS footprint lets 3 (bf16) or 1
+    (fp32) workgroups reside per CU, so the rest of the grid queues behind them and is handed out as
+    tiles stop early; the factor 4 is an unmeasured tuning constant, not a residency figure."""
+    waves = 4 if prec_code == 2 else 8
+    tiles = (BN + 1) // 2
+    return max(1, min((tiles + waves - 1) // waves, 4 * num_cu(device)))
+
+
+def refine_local(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, ctl, *, loops, lr,
+                 prec=None, hn_out=None, flag_out=None, num_blocks=None, env_active=None, a_max=None):
+    """The decentralised safety filter (csrc/refine.hip refine_local_kernel, ``evaluate.py``'s module
+    docstring): every agent refines its own action against its neighbours' nominal next states, the whole
+    loop in ONE launch for any scene. Arguments as for ``refine`` without dEv and the reverse CSR; delta
+    (B, N, D) must be ZERO on entry; ctl int64, >= 2*loops words, cleared by the driver, holds the loop
+    path's control words afterwards (ctl[2 it] exactly; ctl[2 it + 1] is the violation sum of iteration it
+    for every it, also after the stop). Bit for bit the results of ``refine(..., local=True)``. Returns the
+    workgroup count. No host synchronisation. fp32 (x3) and bf16 builds; fp16 is not supported."""
+    # what needs no device first: the precision, the loop count
+    if _half(wpack, "wpack", prec) == 1:
+        raise NativeError("safety filter: fp16 is not supported (the -1 upstream gradient has no loss scaling); "
+                          "use fp32 or bf16")
+    if int(loops) < 0:
+        raise NativeError("loops must be >= 0")
+    if ctl is None:
+        raise NativeError("ctl is required")
+    B, N, Nn, K, D, loops, code, kw = _refine_args(S, idx, a, delta, h, wpack, f_bwd, wrm, wvec, None, None, loops, prec,
+                                                   hn_out, flag_out, env_active, lr, a_max, local=True)
+    check(ctl, torch.int64, None, "ctl")
+    if ctl.dim() != 1 or ctl.numel() < 2 * loops:
+        raise NativeError(f"ctl must be int64 with at least 2*loops = {2 * loops} words, got {tuple(ctl.shape)}")
+    if B * N * 16 >= 2 ** 31 - 2 ** 21:
+        raise NativeError("too many agents for 32-bit indexing")
+    nb = int(num_blocks) if num_blocks else refine_local_grid(B * N, S.device, code)
+    if nb < 1 or nb > 4096:
+        raise NativeError("num_blocks outside 1..4096")
+    _ok(lib().refine_local(loops=loops, fused=1, fused_blocks=nb, prec=code, stream=stream_handle(), ctl=ptr(ctl), **kw),
+        "refine_local")
     return nb
 
 
@@ -1594,7 +1648,7 @@ def episode_final(S_cur, G, st, dist_fx, safe, active, prev_active, out):
 
 
 def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask_done, persistent, ctrl, cbf,
-                a_max=None):
+                a_max=None, local=False, fused=False):
     """A whole batch of closed-loop episodes as one native call (csrc/runtime.cpp EpisodeDriver).
 
     buf: the call's device buffers (ops/episode.py allocates them): S0 / S1 (B, Nn, 4|8) record
@@ -1608,12 +1662,19 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     per-axis actuator limit (the controller's actions are clamped in place, the filter projects, the
     applied action is clamped). buf may hold act_st (EP_ACT_WORDS,) int64 zero and act_out
     (EP_ACT_WORDS,) int64, both or neither: the action statistics (evaluate.ACTION_STATS).
+    local: the decentralised filter (``evaluate.py``'s module docstring) -- no rptr / redges, never
+    persistent, the loop filter's ctl; fused (local only): one refine_local launch per step, no dEv.
     Returns (steps issued, index of the record buffer that holds the final state)."""
     K, max_steps, check_every, loops = int(K), int(max_steps), int(check_every), int(loops)
     if K < 1 or K > C.MAX_TOP_K:
         raise NativeError(f"K = {K} outside 1..{C.MAX_TOP_K}")
     if max_steps < 0 or check_every < 1 or loops < 0:
         raise NativeError("max_steps >= 0, check_every >= 1 and loops >= 0 are required")
+    local, fused = bool(local), bool(fused)
+    if local and persistent:
+        raise NativeError("the persistent filter has no local coupling")
+    if fused and not local:
+        raise NativeError("the fused filter is the local coupling's")
     # what needs no device first: K, the loop counts, the filter's precision
     qc = 0
     bw = bv = brm = bmp = None
@@ -1660,9 +1721,10 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
         _ep(brm, bw.dtype, (_planes(qc) * (128 * 68 + 64 * 148),), "CBF wrm")
         _ep(buf.get("delta"), torch.float32, (B, N, D), "delta")
         _ep(buf.get("h"), torch.float32, (B, N, K), "h")
-        _ep(buf.get("rptr"), torch.int32, (B, Nn + 1), "rptr")
-        _ep(buf.get("redges"), torch.int32, (B, N * K), "redges")
-        if B * N * K >= 2 ** 31 - 2 ** 21:
+        if not local:
+            _ep(buf.get("rptr"), torch.int32, (B, Nn + 1), "rptr")
+            _ep(buf.get("redges"), torch.int32, (B, N * K), "redges")
+        if B * N * (16 if fused else K) >= 2 ** 31 - 2 ** 21:
             raise NativeError("too many edges for 32-bit indexing")
         if persistent:
             if not refine_small_eligible(Nn, K):
@@ -1670,7 +1732,8 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
             _ep(buf.get("ew"), torch.int64, (B, loops, 2), "ew")
         else:
             _ep(buf.get("ctl"), torch.int64, (2 * loops,), "ctl")
-            _ep(buf.get("dEv"), torch.float32, (B, N, K, D), "dEv")
+            if not fused:
+                _ep(buf.get("dEv"), torch.float32, (B, N, K, D), "dEv")
     _ep_device(**{k: t for k, t in buf.items() if isinstance(t, torch.Tensor)}, ctrl_wpack=cw, ctrl_wvec=cv,
                cbf_wpack=bw, cbf_wvec=bv, cbf_wrm=brm)
     dev = S0.device
@@ -1683,9 +1746,13 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     ep.update(A=ptr(g("A")), delta=ptr(g("delta") if filt else None), ctl=ptr(g("ctl") if mode == 1 else None),
               ew=ptr(g("ew") if mode == 2 else None), loops=loops, mode=mode, out=ptr(g("out")), **limit_kw)
     # the filter's arguments (S: per step; the mask is dropped by the driver unless mask_done)
-    flt = _refine_kw(B, N, Nn, K, D, None, g("idx"), g("A"), g("delta"), g("h"), bw, bmp.off["w1f"], brm, bv, g("rptr"),
-                     g("redges"), lr, env_active=g("active"), a_max=a_max, dEv=ptr(g("dEv") if mode == 1 else None), ctl=ep["ctl"],
-                     ew=ep["ew"], loops=loops, num_blocks=refine_grid(E, dev, qc), prec=qc) if filt else None
+    loc = {}
+    if local:
+        loc = dict(local=1, fused=int(fused), fused_blocks=refine_local_grid(B * N, dev, qc))
+    flt = _refine_kw(B, N, Nn, K, D, None, g("idx"), g("A"), g("delta"), g("h"), bw, bmp.off["w1f"], brm, bv,
+                     None if local else g("rptr"), None if local else g("redges"), lr, env_active=g("active"), a_max=a_max,
+                     dEv=ptr(g("dEv") if mode == 1 and not fused else None), ctl=ep["ctl"],
+                     ew=ep["ew"], loops=loops, num_blocks=refine_grid(E, dev, qc), prec=qc, **loc) if filt else None
     # the step's launches on S0 (the driver swaps the record buffers): one scan with the kNN lists and the
     # safety count, the safety-only scan of the final state, the controller, and the filter's h(s_t) and CSR
     cs, sc = _scan_kw(S0, g("idx"), None, None, g("safe"), K=K, perm=g("perm"), n_agents=N)
@@ -1697,7 +1764,7 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
         cbf_kw, _, nb = _cbf_fwd_kw(S0[None], g("idx")[None], bw, bmp.off["w1f"], bv, two=False, h_out=g("h")[None],
                                     prec=bmp.prec)
     cfg = dict(episode=ep, refine=flt, cell_sort=cs, scan=sc, scan_final=fin, ctrl=ck, cbf=cbf_kw,
-               csr=_rev_csr_kw(g("idx"), g("rptr"), g("redges"), Nn) if filt else None, S1=ptr(g("S1")), num_cu=ncu,
+               csr=_rev_csr_kw(g("idx"), g("rptr"), g("redges"), Nn) if filt and not local else None, S1=ptr(g("S1")), num_cu=ncu,
                prec_ctrl=pc, cbf_blocks=nb, max_steps=max_steps, check_every=check_every,
                mask_done=int(bool(mask_done)), stream=stream_handle())
     try:

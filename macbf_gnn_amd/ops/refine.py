@@ -28,6 +28,15 @@ of at most 32 graph nodes; docs/PERF.md, "Persistent filter") and the loop every
 clamped with a torch op before the launches, both update kernels project ``delta`` onto
 [-a_max - a_c, a_max - a_c] after every step (behind one scalar test: without a limit they run the
 instructions they always ran), and the result is clamp(a_c + delta, -a_max, a_max).
+
+``coupling`` (opt-in; ``evaluate.py``'s module docstring states the rule): ``"joint"`` is the filter
+above. ``"local"`` is the decentralised filter -- every agent refines its own action against its
+neighbours' nominal next states -- with two implementations of its own, bit for bit the same results:
+``"fused"`` (``refine_local_kernel``: a 2-agent x 16-slot tile runs its whole loop in one wave, delta in
+registers, one launch for any scene; the default) and ``"loop"`` (``refine_grad_local_kernel`` /
+``refine_update_local_kernel``: the loop path's instantiations without the neighbour's delta and the
+in-edge sum). Neither builds a reverse CSR. The persistent filter has no local variant, and the fused
+kernel no joint one: both pairs are errors that name the option.
 """
 from __future__ import annotations
 
@@ -35,12 +44,18 @@ import torch
 
 from .. import config as C
 from .. import knobs
-from ..evaluate import check_a_max
+from ..evaluate import COUPLINGS, check_a_max
 from . import graph, native
 from .packing import module_pack
 
 
 IMPLS = (None, "loop", "persistent")
+LOCAL_IMPLS = (None, "fused", "loop")
+# coupling="local", impl=None: precision -> the smallest scene (agents in the batch) from which the loop
+# path is the default. Empty: the fused kernel measured 2.2x (1024 x 4 fp32: 0.78 against 1.73 ms per
+# call) and 2.5x (32 x 8 bf16: 0.28 against 0.68 ms) faster than the loop path (docs/PERF.md,
+# "Decentralised filter").
+AUTO_LOCAL_LOOP = {}
 # impl=None: precision -> the largest env (graph nodes) for which the persistent kernel is the
 # default, i.e. where its minimum beat the loop path's by more than that path's spread
 # (docs/PERF.md, "Persistent filter"): bf16 at 32 nodes (0.50 against 0.71 ms per call); at 64 nodes
@@ -48,9 +63,24 @@ IMPLS = (None, "loop", "persistent")
 AUTO_PERSISTENT = {"bf16": 32}
 
 
-def choose_impl(impl, prec: str, Nn: int, K: int) -> str:
+def choose_impl(impl, prec: str, Nn: int, K: int, coupling: str = "joint", agents: int = 0) -> str:
     """"loop" or "persistent" for a scene of Nn graph nodes per env and K slots (module docstring).
-    An explicit "persistent" on a scene that is not eligible is an error, never a fall-back."""
+    An explicit "persistent" on a scene that is not eligible is an error, never a fall-back.
+    coupling="local": "fused" or "loop" (``agents``: B * N, for ``AUTO_LOCAL_LOOP``)."""
+    if coupling not in COUPLINGS:
+        raise native.NativeError(f"unknown coupling {coupling!r} ('joint' or 'local')")
+    if coupling == "local":
+        if impl == "persistent":
+            raise native.NativeError("impl='persistent' has no local coupling: with coupling='local' use impl='fused', "
+                                     "'loop' or None")
+        if impl not in LOCAL_IMPLS:
+            raise native.NativeError(f"unknown safety-filter impl {impl!r} for coupling='local' (None, 'fused' or 'loop')")
+        if impl is not None:
+            return impl
+        return "loop" if agents >= AUTO_LOCAL_LOOP.get(prec, float("inf")) else "fused"
+    if impl == "fused":
+        raise native.NativeError("unknown safety-filter impl 'fused' for coupling='joint': impl='fused' is the local "
+                                 "coupling's kernel; use impl='loop', 'persistent' or None with coupling='joint'")
     if impl not in IMPLS:
         raise native.NativeError(f"unknown safety-filter impl {impl!r} (None, 'loop' or 'persistent')")
     ok = native.refine_small_eligible(Nn, K)
@@ -67,17 +97,19 @@ def choose_impl(impl, prec: str, Nn: int, K: int) -> str:
 
 def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_LOOPS,
                   lr: float = C.REFINE_LEARNING_RATE, return_trace: bool = False, *, env_active=None,
-                  num_blocks=None, impl=None, a_max=None, return_delta: bool = False):
+                  num_blocks=None, impl=None, a_max=None, return_delta: bool = False, coupling: str = "joint"):
     """s (B, N, 2D), a (B, N, D), idx (B, N, K) on the HIP device, obstacles (B, M, D) or None ->
     (a_refined (B, N, D), used, viol); ``used`` (int64) and ``viol`` (float64) are 0-d device
     tensors -- the caller decides when to read them. ``return_trace=True`` appends a dict with the
     per-iteration active-edge counts ``counts`` (loops,), and ``hn`` (B, N, K) / ``active`` (B, N, K)
     bool of the first iteration (tests). ``env_active`` (B,): envs with False / 0 are not refined
     (module docstring); ``num_blocks`` overrides the workgroup count of the loop path's gradient
-    kernel; ``impl`` None / "loop" / "persistent" (module docstring). ``a_max``: the actuator limit
+    kernel (and of the fused local kernel); ``impl`` None / "loop" / "persistent", with ``coupling="local"``
+    None / "fused" / "loop" (module docstring). ``a_max``: the actuator limit
     (module docstring); the trace dict also holds the raw ``delta`` (B, N, D), and ``return_delta=True``
     appends it as a last element of its own."""
     a_max = check_a_max(a_max)
+    choose_impl(impl, "fp32", 1, 1, coupling)       # an unknown coupling / impl pair: refused before any work
     if not s.is_cuda:
         raise native.NativeError("the safety filter runs on the HIP device")
     if s.dim() != 3 or a.dim() != 3 or idx.dim() != 3:
@@ -107,7 +139,8 @@ def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_L
             a32 = a32.clamp(-a_max, a_max)
         delta = torch.zeros_like(a32)
         h = torch.empty(1, B, N, K, dtype=torch.float32, device=dev)
-        persistent = choose_impl(impl, mp.prec, Nn, K) == "persistent"
+        which = choose_impl(impl, mp.prec, Nn, K, coupling, B * N)
+        persistent, local = which == "persistent", coupling == "local"
         hn = flags = None
         if return_trace:
             hn = torch.zeros(B, N, K, dtype=torch.float32, device=dev)
@@ -120,10 +153,16 @@ def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_L
         if loops > 0:
             native.cbf_fwd(S.view(1, *S.shape), idx32.view(1, B, N, K), w, mp.off["w1f"], v, two=False, h_out=h,
                            prec=mp.prec)
-            rptr = torch.empty(B, Nn + 1, dtype=torch.int32, device=dev)
-            redges = torch.empty(B, N * K, dtype=torch.int32, device=dev)
-            native.rev_csr(idx32, rptr, redges, n_nodes=Nn)
-            if persistent:
+            rptr = redges = None
+            if not local:
+                rptr = torch.empty(B, Nn + 1, dtype=torch.int32, device=dev)
+                redges = torch.empty(B, N * K, dtype=torch.int32, device=dev)
+                native.rev_csr(idx32, rptr, redges, n_nodes=Nn)
+            if which == "fused":
+                native.refine_local(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, ctl, loops=loops,
+                                    lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags, env_active=env_active,
+                                    num_blocks=num_blocks, a_max=a_max)
+            elif persistent:
                 native.refine_small(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, rptr, redges, ew,
                                     loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags,
                                     env_active=env_active, a_max=a_max)
@@ -131,7 +170,7 @@ def safety_filter(cbf_module, s, a, idx, obstacles=None, loops: int = C.REFINE_L
                 dEv = torch.empty(B, N, K, D, dtype=torch.float32, device=dev)
                 native.refine(S, idx32, a32, delta, h.view(B, N, K), w, mp.off["w1f"], rm, v, dEv, rptr, redges, ctl,
                               loops=loops, lr=lr, prec=mp.prec, hn_out=hn, flag_out=flags, env_active=env_active,
-                              num_blocks=num_blocks, a_max=a_max)
+                              num_blocks=num_blocks, a_max=a_max, local=local)
         if persistent:
             used, viol, counts = native.refine_reduce(ew)
         else:

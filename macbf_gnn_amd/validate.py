@@ -32,6 +32,10 @@ the filter projects, and the dict gains ``val_limited_rate``, ``val_refined_limi
 (``ACTION_SUMS``) travel in the same all-reduce, after the existing counts; the largest |u| is left
 out (it would need a second reduction of another kind). Training rollouts are not touched.
 
+``val_refine_coupling="local"`` (``train.py --val_refine_coupling local``; default ``"joint"``) filters
+with the decentralised rule of ``evaluate.py``'s module docstring, with both ``val_impl``s; ``COUNTS``
+and the keys of the dict do not change.
+
 Precision (HIP): the networks run at the training ``dtype``. The filter has no fp16 build (its -1
 upstream gradient has no loss scaling), so a run that trains in fp16 validates both networks in
 bf16. ``validate`` puts ``mfma_dtype`` and the train / eval mode of both modules back, draws from
@@ -46,6 +50,7 @@ import torch
 
 from . import config as C
 from .evaluate import (ACTION_STATS, DELTA_FX, MFMA_DTYPES, _euler, _knn, _safe_count, action_stats, check_a_max,
+                       check_coupling,
                        refine_actions)
 
 VAL_SALT = 0x56414C5345454453          # the validation scenes' seed stream: _mix(cfg.seed, VAL_SALT)
@@ -65,6 +70,13 @@ def default_best_metric(cfg) -> str:
 IMPLS = ("python", "native")
 
 
+def _check_val_coupling(cfg) -> str:
+    try:
+        return check_coupling(getattr(cfg, "val_refine_coupling", "joint"))
+    except ValueError as e:
+        raise ValueError(f"val_refine_coupling: {e}") from None
+
+
 def check_config(cfg, device=None):
     """The validation entries of a TrainConfig that cannot work, reported before the run starts.
     ``device``: the device the run resolved to (``cfg.device`` may be "auto")."""
@@ -81,6 +93,7 @@ def check_config(cfg, device=None):
             check_a_max(a_max)
         except ValueError as e:
             raise ValueError(f"val_a_max must be a positive finite number, or 0 for no limit: {e}") from None
+    _check_val_coupling(cfg)
     if cfg.val_every < 0 or cfg.val_envs < 1 or cfg.val_refine_loops < 0:
         raise ValueError("val_every must be >= 0, val_envs >= 1 and val_refine_loops >= 0")
     m = default_best_metric(cfg)
@@ -145,6 +158,7 @@ class Validator:
         self.obs = None if obs is None else obs.to(device).clone()
         self.max_steps = int(cfg.inner_loops)
         self.a_max = check_a_max(getattr(cfg, "val_a_max", 0.0) or None)    # the fp32 limit, or None
+        self.coupling = _check_val_coupling(cfg)           # the filter's coupling (evaluate.py)
         self.last_counts: Dict[str, Dict[str, int]] = {}      # the summed integer totals behind the last dict
 
     # ------------------------------------------------------------------ one rollout
@@ -154,14 +168,14 @@ class Validator:
             from .ops import refine as refine_ops
             a, used, _, delta = refine_ops.safety_filter(cbf, s, a, idx, obstacles=self.obs, loops=cfg.val_refine_loops,
                                                          lr=C.REFINE_LEARNING_RATE, env_active=active, a_max=self.a_max,
-                                                         return_delta=True)
+                                                         return_delta=True, coupling=self.coupling)
             return a, used, delta
         delta = torch.zeros_like(a)
         if not bool(active.any()):
             return a, 0, delta
         ar, it, _, dr = refine_actions(cbf, s[active], a[active], idx[active], cfg.val_refine_loops,
                                        C.REFINE_LEARNING_RATE, obstacles=None if self.obs is None else self.obs[active],
-                                       a_max=self.a_max, return_delta=True)
+                                       a_max=self.a_max, return_delta=True, coupling=self.coupling)
         a = a.clone()
         a[active] = ar
         delta[active] = dr
@@ -176,7 +190,7 @@ class Validator:
         if self.impl == "native":
             from .ops import episode
             kw = dict(refine=refine, loops=self.cfg.val_refine_loops, lr=C.REFINE_LEARNING_RATE, max_steps=self.max_steps,
-                      top_k=self.cfg.top_k, mask_done=True, check_every=CHECK_EVERY)
+                      top_k=self.cfg.top_k, mask_done=True, check_every=CHECK_EVERY, coupling=self.coupling)
             if a_max is None:
                 return episode.run_episodes(controller, cbf, s, g, obs, **kw)
             vec, acts = episode.run_episodes(controller, cbf, s, g, obs, a_max=a_max, action_stats=True, **kw)

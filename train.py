@@ -9,7 +9,8 @@ each rank trains ``--num_envs`` environments and gradients are all-reduced over 
 JSON line, with and without the CBF safety filter); ``--save_best`` keeps ``<model_path>.best``;
 ``--val_a_max A`` validates under the actuator limit |u| <= A per axis; ``--a_max A`` trains under it
 (the rollout applies the clamped action, the backward masks the saturated components; the log lines
-gain ``limited_rate``). Neither option follows the other.
+gain ``limited_rate``). Neither option follows the other. ``--val_refine_coupling local`` validates with
+the decentralised filter (every agent refines its own action alone).
 """
 from __future__ import annotations
 
@@ -56,6 +57,9 @@ def parse_args(argv=None):
     p.add_argument("--val_a_max", type=float, default=0.0,
                    help="per-axis actuator limit |u| <= this on the validation rollouts (0: off); adds the limited / "
                         "intervention rates to the validation line")
+    p.add_argument("--val_refine_coupling", type=str, default="joint", choices=["joint", "local"],
+                   help="the validation filter: joint (centralised) or local (every agent refines its own action "
+                        "against its neighbours' nominal next states)")
     p.add_argument("--a_max", type=float, default=0.0,
                    help="per-axis actuator limit |u| <= this on the TRAINING rollouts (0: off): clamp in the rollout, "
                         "mask in the backward; adds limited_rate to the log lines. --val_a_max is set separately")
@@ -75,7 +79,8 @@ def build_config(args):
                         model_path=args.model_path, log_path=args.log_path, dim=args.dim,
                         num_obstacles=args.num_obstacles, graph=args.graph, val_every=args.val_every,
                         val_refine=not args.no_val_refine, save_best=args.save_best, best_metric=args.best_metric,
-                        val_impl=args.val_impl, val_a_max=args.val_a_max, a_max=args.a_max)
+                        val_impl=args.val_impl, val_a_max=args.val_a_max, a_max=args.a_max,
+                        val_refine_coupling=args.val_refine_coupling)
     for name in ("train_steps", "inner_loops", "top_k", "lr", "display_steps", "save_steps", "val_envs",
                  "val_refine_loops"):
         v = getattr(args, name)
