@@ -75,6 +75,18 @@ def tie_log(what, ties, total, limit):
     assert ties <= limit, f"{what}: {ties} tie rows of {total} > allowance {limit}"
 
 
+def ratio_log(what, ratios):
+    """Worst err / bound ratios of a check against a derived bound (a dict name -> ratio; the bound
+    itself is asserted by the caller): printed, and with MACBF_NUM_LOG appended as one JSON line."""
+    print("RATIO", what, " ".join(f"{k}={v:.4g}" for k, v in ratios.items()))
+    log = os.environ.get("MACBF_NUM_LOG")
+    if log:
+        with open(log, "a") as f:
+            f.write(json.dumps({"test": os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0], "name": what,
+                                "err": max(float(v) for v in ratios.values()), "cos": 1.0, "bound": 1.0,
+                                "ratios": {k: float(v) for k, v in ratios.items()}}) + "\n")
+
+
 def _lin64(x, w, b):
     w = w.detach().double()
     w = w.reshape(w.shape[0], -1)
