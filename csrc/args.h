@@ -97,6 +97,10 @@ struct CtrlArgs {
   // per-axis actuator limit of the training rollout (0: off): the Euler step applies
   // clamp(a, -a_max, a_max); A, act_sum and the backward keep the raw action (oracle.py)
   float a_max;
+  // residual head (0: off): the last node layer has 3D real rows and a_q += y4[2D + q] before the
+  // noise (oracle.py, "Residual head"). Selects the *_res_kernel instantiations. (Sits in the struct's
+  // tail padding: the kernels' argument size does not change.)
+  int res;
 };
 
 // Persistent small-scene rollout (ctrl.hip rollout_small_kernel): one workgroup per env runs
@@ -319,6 +323,9 @@ struct CtrlNodeBwdArgs {
   // the rollout's actuator limit (0: off): dL/da through the Euler step is zero where the raw
   // action A lies outside [-a_max, a_max] or is NaN (state.h limit_adjoint)
   float a_max;
+  // residual head (0: off): dL/dy4[2D + q] = da_q (oracle.py, "Residual head"). Selects the
+  // *_res_kernel instantiations. (Tail padding: the argument size does not change.)
+  int res;
 };
 
 struct CtrlEdgeBwdArgs {

@@ -298,7 +298,10 @@ DEV void edge_rel(const EdgeSt<D>& c, float (&rp)[D], float (&rv)[D]) {
 // the fused x3 step kernel spill where they are not wanted)
 // LIM: the actuator limit (a.a_max != 0) is an instantiation of its own, so the limit-off kernels
 // are the code they were (docs/PERF.md)
-template <int D, bool ACTS, bool LIM, typename PoolFr>
+// RES: the residual head (a.res != 0; macbf_gnn_amd/oracle.py, "Residual head"), again an instantiation
+// of its own: a_q += y4 row 2D + q before the noise. Under RES the limit is the scalar a.a_max != 0 test
+// (LIM stays false: one residual kernel serves both, docs/ARCHITECTURE.md "Residual head")
+template <int D, bool ACTS, bool LIM, bool RES, typename PoolFr>
 DEV void node_phase(const CtrlArgs& a, int g0, int APW, int total, PoolFr pool, const h16* wn, const float* nb2,
                     const float* nb3, const float* nb4, int lane) {
   const int r = lane & 31, h = lane >> 5;
@@ -342,6 +345,9 @@ DEV void node_phase(const CtrlArgs& a, int g0, int APW, int total, PoolFr pool, 
       const float kp = 2.f / (1.f + __expf(-y4r[2 * q])) + 0.2f;
       const float kv = 2.f / (1.f + __expf(-y4r[2 * q + 1])) + 0.2f;
       av[q] = -(kp * ex[q] + kv * sv[q]);
+      // residual rows 2D..3D-1: rows 4..7 come with acc_rows8; row 8 (D = 3, q = 2) is register 4 of
+      // this h == 0 lane
+      if constexpr (RES) av[q] += (2 * D + q < 8) ? y4r[(2 * D + q) & 7] : na.Y4[4];
       if (a.noise) av[q] += a.noise[((long)b * a.n_env + i) * D + q];
     }
     if (a.noise_key) {
@@ -368,6 +374,7 @@ DEV void node_phase(const CtrlArgs& a, int g0, int APW, int total, PoolFr pool, 
     for (int q = 0; q < D; ++q) {
       snp[q] = sp[q] + sv[q] * a.dt;
       if constexpr (LIM) snv[q] = sv[q] + limit_action(av[q], a.a_max) * a.dt;
+      else if constexpr (RES) snv[q] = sv[q] + (a.a_max != 0.f ? limit_action(av[q], a.a_max) : av[q]) * a.dt;
       else snv[q] = sv[q] + av[q] * a.dt;
       ar[q] = -(ex[q] + a.sqrt3 * sv[q]);
     }
@@ -539,7 +546,8 @@ constexpr int CTRL_FWD_DENSE = 1;
 // 0 weight staging (from t0, the kernel start), 1 group prologue loads, per edge tile 2 load issue,
 // 3 edge features, 4 edge MLP, 5 pool + stores; 6 pooled-store wait, 7 node phase; 15 tile count
 // (scripts/stamps_ctrl.py). A separate instantiation: no runtime stamp branches in production.
-template <int D, bool SPLIT, bool GNODE = false, bool DENSE12 = false, bool ST = false, bool ACTS = false, bool LIM = false>
+template <int D, bool SPLIT, bool GNODE = false, bool DENSE12 = false, bool ST = false, bool ACTS = false, bool LIM = false,
+          bool RES = false>
 DEV void ctrl_fwd_groups(const CtrlArgs& a, const h16* wl, const h16* wn, const float* vl, h16* pools, int grp0,
                          int gstride, unsigned long long t0 = 0) {
   constexpr bool GPOOL = X3 || SPLIT;
@@ -674,7 +682,8 @@ DEV void ctrl_fwd_groups(const CtrlArgs& a, const h16* wl, const h16* wn, const 
       int bb, ii;
       agent_bi(ab, gi - g0, N, bb, ii);
       const h16* prow = a.pooled + (long)bb * a.p_env + (long)ii * PROW + 8 * h;
-      node_phase<D, ACTS, LIM>(a, g0, APW, total, [&](int kk) { return row_fr(prow + 16 * kk, 128); }, wn, nb2, nb3, nb4, lane);
+      node_phase<D, ACTS, LIM, RES>(a, g0, APW, total, [&](int kk) { return row_fr(prow + 16 * kk, 128); }, wn, nb2, nb3, nb4,
+                                    lane);
       stamp(7);
       continue;
     }
@@ -692,7 +701,7 @@ DEV void ctrl_fwd_groups(const CtrlArgs& a, const h16* wl, const h16* wn, const 
       }
     }
     // ---------------- node phase: lane column r = agent g0 + r
-    node_phase<D, ACTS, LIM>(a, g0, APW, total, [&](int kk) { return row_fr(pool + r * PSTR + 16 * kk + 8 * h, 0); },
+    node_phase<D, ACTS, LIM, RES>(a, g0, APW, total, [&](int kk) { return row_fr(pool + r * PSTR + 16 * kk + 8 * h, 0); },
                   wn, nb2, nb3, nb4, lane);
     // the pool image is rewritten by the next group: finish all reads first
     lds_wave_sync();
@@ -756,7 +765,7 @@ DEV void publish_step(const CtrlArgs& a) {
 
 // FUSE (x3): all 72 fragments in LDS (145 KB) and the node phase of each group in the same
 // wave right after its edge phase (pooled rows through global memory): one launch per step.
-template <int WAVES, int D, bool FUSE, bool ST, bool ACTS, bool LIM = false>
+template <int WAVES, int D, bool FUSE, bool ST, bool ACTS, bool LIM = false, bool RES = false>
 DEV void ctrl_fwd_body(const CtrlArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   static_assert(FUSE == X3, "the x3 step is the fused one; FUSE stays a parameter for the kernel names");
@@ -776,9 +785,9 @@ DEV void ctrl_fwd_body(const CtrlArgs& a) {
   const int nact = min((int)gridDim.x, (ngrp + WAVES - 1) / WAVES);
   const int lb = (ROLL_XCD && (int)blockIdx.x < nact) ? xcd_block((int)blockIdx.x, nact) : (int)blockIdx.x;
   if (CTRL_FWD_DENSE && a.K == 12 && apw % 8 == 0)
-    ctrl_fwd_groups<D, false, FUSE, true, ST, ACTS, LIM>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
+    ctrl_fwd_groups<D, false, FUSE, true, ST, ACTS, LIM, RES>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
   else
-    ctrl_fwd_groups<D, false, FUSE, false, ST, ACTS, LIM>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
+    ctrl_fwd_groups<D, false, FUSE, false, ST, ACTS, LIM, RES>(a, wl, wn, vl, pools, lb * WAVES + wave_id(), gridDim.x * WAVES, t0);
   publish_step(a);
 }
 
@@ -799,10 +808,16 @@ template <int WAVES, int D, bool FUSE, bool ACTS>
 __global__ __launch_bounds__(WAVES * 64) void ctrl_fwd_lim_kernel(CtrlArgs a) {
   ctrl_fwd_body<WAVES, D, FUSE, false, ACTS, true>(a);
 }
+// the same step with the residual head (a.res != 0; no phase clocks; the limit, if any, by the scalar
+// a.a_max test): a kernel of its own name, the residual-off kernels keep theirs
+template <int WAVES, int D, bool FUSE, bool ACTS>
+__global__ __launch_bounds__(WAVES * 64) void ctrl_fwd_res_kernel(CtrlArgs a) {
+  ctrl_fwd_body<WAVES, D, FUSE, false, ACTS, false, true>(a);
+}
 
 // Node phase of the controller step over the pooled rows in global memory, 32-agent groups
 // grp0, grp0 + gstride, ... (the persistent small-scene rollout)
-template <int D, bool ACTS = false, bool LIM = false>
+template <int D, bool ACTS = false, bool LIM = false, bool RES = false>
 DEV void ctrl_node_groups(const CtrlArgs& a, const h16* wn, const float* vl, int grp0, int gstride) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const int N = a.N;
@@ -812,7 +827,7 @@ DEV void ctrl_node_groups(const CtrlArgs& a, const h16* wn, const float* vl, int
     const int gi = min(g0 + r, total - 1);
     const int b = gi / N, i = gi - b * N;
     const h16* prow = a.pooled + (long)b * a.p_env + (long)i * PROW + 8 * h;
-    node_phase<D, ACTS, LIM>(a, g0, 32, total, [&](int kk) { return row_fr(prow + 16 * kk, 128); }, wn, vl + 128, vl + 256,
+    node_phase<D, ACTS, LIM, RES>(a, g0, 32, total, [&](int kk) { return row_fr(prow + 16 * kk, 128); }, wn, vl + 128, vl + 256,
                   vl + 320, lane);
   }
 }
@@ -844,7 +859,10 @@ extern "C" int MB_SYM(ctrl_fwd)(const mb::CtrlArgs* a, int num_cu, hipStream_t s
   // (x3: 4-wave workgroups for the slices' small grids -- one wave per SIMD on twice the CUs --
   // measured no faster: 8-env slice 2.825-2.833 vs 2.797-2.820 ms, profiles/r6b/)
   auto go = [&](auto kern) { return launch_lds(kern, dim3(blocks), dim3(CTRL_WAVES * 64), ctrl_fwd_lds(), st, b); };
+  // ranking: residual (carries the limit itself), then limit, then stamps (x3), then acts
   return by_dim(a->dim, [&](auto D) {
+    if (a->res)               // the residual head: its own instantiations (no phase clocks)
+      return by_flag(a->acts != nullptr, [&](auto ACTS) { return go(ctrl_fwd_res_kernel<CTRL_WAVES, D(), X3, ACTS()>); });
     if (a->a_max != 0.f)
       return by_flag(a->acts != nullptr, [&](auto ACTS) { return go(ctrl_fwd_lim_kernel<CTRL_WAVES, D(), X3, ACTS()>); });
     if constexpr (X3)       // phase clocks: the x3 step only
@@ -1005,7 +1023,9 @@ DEV void fused_combine(const CtrlNodeBwdArgs& a, bool ok, int b, int i, int h, f
 // P: this workgroup's slab row)
 // LIM: the rollout's actuator limit (a.a_max != 0) is its own instantiation of the node-backward
 // kernels, so the limit-off kernels are the code they were (registers, schedule: docs/PERF.md)
-template <int D, bool LIM>
+// RES: the residual head (a.res != 0): dL/dy4[2D + q] = da_q, again its own instantiation; it takes the
+// limit by limit_adjoint's own scalar a_max != 0 test (LIM stays false)
+template <int D, bool LIM, bool RES = false>
 DEV void node_bwd_body(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, long cstride, float* P) {
   constexpr int RM = (X3 ? 2 : 1) * NODE_RM_ELEMS;
   h16* wr = reinterpret_cast<h16*>(smem);
@@ -1138,7 +1158,7 @@ constexpr int NB_PREFETCH = 1;
     //      regs 0..3 of lane r and (D = 3) regs 0,1 of lane r + 32)
     float y4r[8];
     acc_rows8(y4, y4r);
-    float d4r[8];
+    float d4r[8], d4r8 = 0.f;
 #pragma unroll
     for (int q = 0; q < 8; ++q) d4r[q] = 0.f;
     float egp[D], egv[D];                         // dL/d(p - g), dL/dv of the ego terms
@@ -1148,7 +1168,7 @@ constexpr int NB_PREFETCH = 1;
       float da[D], ar[D];
 #pragma unroll
       for (int q = 0; q < D; ++q) { da[q] = a.dt * gnv[q]; ar[q] = -(ex[q] + a.sqrt3 * sv[q]); }
-      if constexpr (LIM) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
+      if constexpr (LIM || RES) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
       float act_coef = a.act_scale ? a.act_coef / fmaxf(*a.act_scale, 1.f) : a.act_coef;
       if (a.gscale) act_coef *= *a.gscale;        // fp16: device loss scale
       if (vld && act_coef != 0.f) {
@@ -1171,6 +1191,11 @@ constexpr int NB_PREFETCH = 1;
         egv[q] += -kv * da[q];
         d4r[2 * q] = -da[q] * ex[q] * 2.f * s0 * (1.f - s0);
         d4r[2 * q + 1] = -da[q] * sv[q] * 2.f * s1 * (1.f - s1);
+        // residual rows 2D + q: dL/dy4 = da (row 8, D = 3: register 4 of this h == 0 lane)
+        if constexpr (RES) {
+          if (2 * D + q < 8) d4r[(2 * D + q) & 7] = da[q];
+          else d4r8 = da[q];
+        }
       }
     }
     // back to the accumulator layout: rows 0..3 -> regs 0..3 of h = 0, rows 4..7 -> of h = 1
@@ -1180,6 +1205,7 @@ constexpr int NB_PREFETCH = 1;
       const float hi4 = shfl_xor32(d4r[4 + q]);
       d4[q] = (h == 0) ? d4r[q] : hi4;
     }
+    if constexpr (RES && D == 3) d4[4] = d4r8;
     const Pk d4b = to_pk(d4);
     // Backward chain interleaved with the WG-shared weight-gradient stages so that each
     // activation dies right after its last use (register pressure). A stage runs in NB_NT
@@ -1401,7 +1427,7 @@ constexpr int NB_PREFETCH = 1;
 constexpr int NC_SW = 296;                           // 148 dwords: row reads spread over the banks
 static_assert(NC_SW * 32 <= NB_PL, "cooperative region must fit the stage plane");
 
-template <int D, bool LIM>
+template <int D, bool LIM, bool RES = false>
 DEV void node_bwd_coop(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, long cstride, float* P) {
   constexpr int RM = (X3 ? 2 : 1) * NODE_RM_ELEMS;
   constexpr int SW = NC_SW, PLN = NB_PL;
@@ -1573,14 +1599,14 @@ DEV void node_bwd_coop(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, l
       }
       float y4r[8];
       acc_rows8(y4, y4r);
-      float d4r[8];
+      float d4r[8], d4r8 = 0.f;
 #pragma unroll
       for (int q = 0; q < 8; ++q) d4r[q] = 0.f;
       if (ok && h == 0) {
         float da[D], ar[D];
 #pragma unroll
         for (int q = 0; q < D; ++q) { da[q] = a.dt * gnv[q]; ar[q] = -(ex[q] + a.sqrt3 * sv[q]); }
-        if constexpr (LIM) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
+        if constexpr (LIM || RES) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
         float act_coef = a.act_scale ? a.act_coef / fmaxf(*a.act_scale, 1.f) : a.act_coef;
         if (a.gscale) act_coef *= *a.gscale;
         if (vld && act_coef != 0.f) {
@@ -1602,6 +1628,11 @@ DEV void node_bwd_coop(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, l
           egv[q] += -kv * da[q];
           d4r[2 * q] = -da[q] * ex[q] * 2.f * s0 * (1.f - s0);
           d4r[2 * q + 1] = -da[q] * sv[q] * 2.f * s1 * (1.f - s1);
+          // residual rows 2D + q: dL/dy4 = da (row 8, D = 3: register 4 of this h == 0 lane)
+          if constexpr (RES) {
+            if (2 * D + q < 8) d4r[(2 * D + q) & 7] = da[q];
+            else d4r8 = da[q];
+          }
         }
       }
       f32x16 d4 = zero16();
@@ -1610,6 +1641,7 @@ DEV void node_bwd_coop(const CtrlNodeBwdArgs& a, unsigned char* smem, long c0, l
         const float hi4 = shfl_xor32(d4r[4 + q]);
         d4[q] = (h == 0) ? d4r[q] : hi4;
       }
+      if constexpr (RES && D == 3) d4[4] = d4r8;
       store_pk(stg, SW, r, 192, to_pk(d4), h, PLN);
     }
     __syncthreads();
@@ -1774,6 +1806,12 @@ __global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_node_bwd_lim_kernel(Ctr
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   node_bwd_body<D, true>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
 }
+// with the residual head (a.res != 0): kernels of their own names, the residual-off kernels keep theirs
+template <int D>
+__global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_node_bwd_res_kernel(CtrlNodeBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  node_bwd_body<D, false, true>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+}
 
 // separate kernel: one shared body would size both paths' registers for the larger (spills)
 template <int D>
@@ -1785,6 +1823,11 @@ template <int D>
 __global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_node_bwd_coop_lim_kernel(CtrlNodeBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   node_bwd_coop<D, true>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+}
+template <int D>
+__global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_node_bwd_coop_res_kernel(CtrlNodeBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  node_bwd_coop<D, false, true>(a, smem, blockIdx.x, gridDim.x, a.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2137,6 +2180,15 @@ __global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_bwd_step_lim_kernel(Ctr
   __syncthreads();                                      // (and the node phase's LDS reads done)
   edge_bwd_body<D, KC, true>(ea, smem, blockIdx.x, gridDim.x, ea.partial + (long)blockIdx.x * CTRL_EDGE_PARTIAL);
 }
+// the same step with the residual head (a kernel of its own name)
+template <int D, int KC>
+__global__ __launch_bounds__(NB_WAVES * 64, 1) void ctrl_bwd_step_res_kernel(CtrlNodeBwdArgs na, CtrlEdgeBwdArgs ea) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  node_bwd_coop<D, false, true>(na, smem, blockIdx.x, gridDim.x, na.partial + (long)blockIdx.x * CTRL_NODE_PARTIAL);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this workgroup's dP / ego stores complete
+  __syncthreads();                                      // (and the node phase's LDS reads done)
+  edge_bwd_body<D, KC, true>(ea, smem, blockIdx.x, gridDim.x, ea.partial + (long)blockIdx.x * CTRL_EDGE_PARTIAL);
+}
 
 // =======================================================================================
 // Persistent small-scene rollout (envs of <= SMALL_MAXN graph nodes; reference train.py:58-81).
@@ -2262,7 +2314,7 @@ DEV void small_scan(const RolloutSmallArgs& ra, const float4* Sb, int N, int Nn,
   }
 }
 
-template <int D, bool ACTS, bool LIM>
+template <int D, bool ACTS, bool LIM, bool RES = false>
 DEV void rollout_small_body(RolloutSmallArgs ra) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ SmallScanLds L;
@@ -2349,7 +2401,7 @@ DEV void rollout_small_body(RolloutSmallArgs ra) {
     stamp(1);
     __syncthreads();                                // the env's pooled rows -> node phase
     stamp(2);
-    ctrl_node_groups<D, ACTS, LIM>(e, wn, vl, wave, SR_WAVES);
+    ctrl_node_groups<D, ACTS, LIM, RES>(e, wn, vl, wave, SR_WAVES);
     stamp(3);
     // s_{t+1} (read by this workgroup only) and the env's sum atomics (device scope) complete
     // before the barrier; the workgroup-scope barrier is enough for both
@@ -2397,6 +2449,11 @@ template <int D, bool ACTS>
 __global__ __launch_bounds__(SR_WAVES * 64) void rollout_small_lim_kernel(RolloutSmallArgs ra) {
   rollout_small_body<D, ACTS, true>(ra);
 }
+// with the residual head (c.res != 0; the limit, if any, by the scalar c.a_max test): a kernel of its own name
+template <int D, bool ACTS>
+__global__ __launch_bounds__(SR_WAVES * 64) void rollout_small_res_kernel(RolloutSmallArgs ra) {
+  rollout_small_body<D, ACTS, false, true>(ra);
+}
 
 size_t rollout_small_lds() { return (size_t)CTRL_FWD_FRAGS * FRAG_SZ + CTRL_VEC * 4; }
 
@@ -2423,6 +2480,8 @@ extern "C" int MB_SYM(ctrl_node_bwd)(const mb::CtrlNodeBwdArgs* a, int num_block
   b.coop = a->chunk == 32;     // 32-agent chunks: the four waves cooperate (node_bwd_coop)
   auto go = [&](auto kern) { return launch_lds(kern, dim3(num_blocks), dim3(NB_WAVES * 64), ctrl_node_bwd_lds(), st, b); };
   return by_dim(a->dim, [&](auto D) {
+    if (a->res)               // the residual head: its own instantiations (they carry the limit themselves)
+      return b.coop ? go(ctrl_node_bwd_coop_res_kernel<D()>) : go(ctrl_node_bwd_res_kernel<D()>);
     if (a->a_max != 0.f)      // the actuator limit: its own instantiations
       return b.coop ? go(ctrl_node_bwd_coop_lim_kernel<D()>) : go(ctrl_node_bwd_lim_kernel<D()>);
     return b.coop ? go(ctrl_node_bwd_coop_kernel<D()>) : go(ctrl_node_bwd_kernel<D()>);
@@ -2465,6 +2524,7 @@ extern "C" int MB_SYM(ctrl_bwd_step)(const mb::CtrlNodeBwdArgs* na, const mb::Ct
   auto go = [&](auto kern) { return launch_lds(kern, dim3(num_blocks), dim3(NB_WAVES * 64), lds, st, n, e); };
   return by_dim(ea->dim, [&](auto D) {
     return by_k12(ea->K, [&](auto KC) {
+      if (na->res) return go(ctrl_bwd_step_res_kernel<D(), KC()>);               // the residual head (carries the limit itself)
       if (na->a_max != 0.f) return go(ctrl_bwd_step_lim_kernel<D(), KC()>);      // the actuator limit: its own instantiations
       return go(ctrl_bwd_step_kernel<D(), KC()>);
     });
@@ -2481,6 +2541,7 @@ extern "C" int MB_SYM(rollout_small)(const mb::RolloutSmallArgs* a, hipStream_t 
   auto go = [&](auto kern) { return launch_lds(kern, dim3(c.B), dim3(SR_WAVES * 64), rollout_small_lds(), st, *a); };
   return by_dim(c.dim, [&](auto D) {
     return by_flag(c.acts != nullptr, [&](auto ACTS) {
+      if (c.res) return go(rollout_small_res_kernel<D(), ACTS()>);               // the residual head (carries the limit itself)
       if (c.a_max != 0.f) return go(rollout_small_lim_kernel<D(), ACTS()>);
       return go(rollout_small_kernel<D(), ACTS()>);
     });

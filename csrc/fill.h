@@ -33,6 +33,7 @@ inline mb::CtrlArgs ctrl_args(Args& x) {
   x("noise_scale", a.noise_scale); x("noise_t", a.noise_t); x("dt", a.dt); x("obs_r", a.obs_r); x("sqrt3", a.sqrt3);
   x("pooled", a.pooled); x("p_env", a.p_env); x("argmax", a.argmax); x("am_env", a.am_env); x("apw", a.apw);
   x("stamps", a.stamps); x.opt("a_max", a.a_max);      // the actuator limit: off (0) without the key
+  x.opt("res", a.res);                                  // the residual head: off (0) without the key
   return a;
 }
 
@@ -80,7 +81,7 @@ inline mb::CtrlNodeBwdArgs node_bwd_args(Args& x) {
   x.opt("cds_env", a.cds_env); x.opt("cego", a.cego); x.opt("cdEc", a.cdEc); x.opt("cptr", a.cptr);
   x.opt("cptr_env", a.cptr_env); x.opt("cedges", a.cedges); x.opt("cedges_env", a.cedges_env); x.opt("cGn", a.cGn);
   x.opt("cgn_env", a.cgn_env); x.opt("cGout", a.cGout); x.opt("cgo_env", a.cgo_env); x.opt("K", a.K);
-  x("stamps", a.stamps); x.opt("a_max", a.a_max);
+  x("stamps", a.stamps); x.opt("a_max", a.a_max); x.opt("res", a.res);
   return a;
 }
 

@@ -109,11 +109,15 @@ DEV Fr n16_w1T(const h16* W, int m0, int s, int lane) {
 // the production fp32 kernel two more spilled registers (docs/PERF.md); it rides on the first
 // parameter because the limit-off kernels must stay the code, and keep the names (<D, ST>), they had:
 // a body shared by two kernels compiled to other register counts.
-constexpr int N16_LIM = 4;
+// N16_RES: the instantiation for the residual head (a.res != 0; macbf_gnn_amd/oracle.py, "Residual
+// head"): dL/dy4[2D + q] = da_q. It rides on the first parameter for the same reason, and takes the limit
+// by limit_adjoint's own scalar a_max != 0 test (N16_LIM stays off under it).
+constexpr int N16_LIM = 4, N16_RES = 8;
 template <int DL, bool ST>
 __global__ __launch_bounds__(N16_NW * 64) void ctrl_node_bwd16_kernel(CtrlNodeBwdArgs a) {
   constexpr int D = DL & 3;
   constexpr bool LIM = (DL & N16_LIM) != 0;
+  constexpr bool RES = (DL & N16_RES) != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   h16* W1 = reinterpret_cast<h16*>(smem);
   float* vl = reinterpret_cast<float*>(smem + N16_LDS_W);
@@ -242,7 +246,7 @@ __global__ __launch_bounds__(N16_NW * 64) void ctrl_node_bwd16_kernel(CtrlNodeBw
     float y4r[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q) { y4r[q] = y4[q]; y4r[4 + q] = lane_xorf<16>(y4[q]); }
-    float d4r[8];
+    float d4r[8], d4r8 = 0.f;
 #pragma unroll
     for (int q = 0; q < 8; ++q) d4r[q] = 0.f;
     float egp[D], egv[D];                         // dL/d(p - g), dL/dv of the ego terms
@@ -252,7 +256,7 @@ __global__ __launch_bounds__(N16_NW * 64) void ctrl_node_bwd16_kernel(CtrlNodeBw
       float da[D], ar[D];
 #pragma unroll
       for (int q = 0; q < D; ++q) { da[q] = a.dt * gnv[q]; ar[q] = -(ex[q] + a.sqrt3 * sv[q]); }
-      if constexpr (LIM) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
+      if constexpr (LIM || RES) limit_adjoint<D>(da, av, a.a_max);     // the clamp's adjoint, before the action-loss term
       float act_coef = a.act_scale ? a.act_coef / fmaxf(*a.act_scale, 1.f) : a.act_coef;
       if (a.gscale) act_coef *= *a.gscale;
       if (vld && act_coef != 0.f) {
@@ -274,14 +278,23 @@ __global__ __launch_bounds__(N16_NW * 64) void ctrl_node_bwd16_kernel(CtrlNodeBw
         egv[q] += -kv * da[q];
         d4r[2 * q] = -da[q] * ex[q] * 2.f * s0 * (1.f - s0);
         d4r[2 * q + 1] = -da[q] * sv[q] * 2.f * s1 * (1.f - s1);
+        // residual rows 2D + q: dL/dy4 = da (row 8, D = 3: register 0 of the agent's g == 2 lane)
+        if constexpr (RES) {
+          if (2 * D + q < 8) d4r[(2 * D + q) & 7] = da[q];
+          else d4r8 = da[q];
+        }
       }
     }
-    // back to the C layout: lane (n, g) reg q = d4 row 4g + q (rows >= 2D are zero)
+    // back to the C layout: lane (n, g) reg q = d4 row 4g + q (rows past the layer's real rows are zero)
     f32x4 d4c = zero4();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float hi4 = lane_xorf<16>(d4r[4 + q]);
       d4c[q] = g == 0 ? d4r[q] : (g == 1 ? hi4 : 0.f);
+    }
+    if constexpr (RES && D == 3) {       // row 8: from the g == 0 lane to the g == 2 lane (lanes g = 3 get g = 1's zero)
+      const float r8 = lane_xorf<32>(d4r8);
+      if (g == 2) d4c[0] = r8;
     }
     const Pk4 d4 = to_pk4(d4c);
     Pk4 zp;
@@ -533,6 +546,7 @@ __global__ __launch_bounds__(N16_NW * 64) void ctrl_node_bwd16_kernel(CtrlNodeBw
 template <int D>
 static int launch_ctrl_node_bwd16(const CtrlNodeBwdArgs& a, int num_blocks, hipStream_t st) {
   auto go = [&](auto kern) { return launch_lds(kern, dim3(num_blocks), dim3(N16_NW * 64), N16_LDS, st, a); };
+  if (a.res) return go(ctrl_node_bwd16_kernel<D | N16_RES, false>);      // the residual head (carries the limit itself; no phase clocks)
   if (a.a_max != 0.f) return go(ctrl_node_bwd16_kernel<D | N16_LIM, false>);      // (no phase clocks under the limit)
   return by_flag(a.stamps != nullptr, [&](auto ST) { return go(ctrl_node_bwd16_kernel<D, ST()>); });
 }

@@ -4,7 +4,7 @@
                        [--max_steps 50] [--no_refine] [--refine_space actions|gains] [--diagnose]
                        [--dim 2|3] [--num_obstacles M] [--dtype fp32|bf16|fp16]
                        [--refine_impl autograd|native] [--rollout_impl python|native]
-                       [--a_max A] [--action_stats] [--refine_coupling joint|local]
+                       [--a_max A] [--action_stats] [--refine_coupling joint|local] [--ctrl_residual]
                        [--device auto|cpu|hip] [--gpu 0]
 
 Prints one JSON line: safety rate, reaching rate, mean final goal distance, refinement
@@ -21,6 +21,9 @@ the filter projects onto the box; not with --diagnose or --refine_space gains) a
 --action_stats alone, adds limited_rate, intervention_rate, mean_abs_delta and max_abs_action.
 --refine_coupling local runs the decentralised filter: every agent refines its own action against its
 neighbours' nominal next states (not with --refine_space gains).
+The controller is built as the checkpoint holds it: with the residual head where its last node layer
+has 3D rows. --ctrl_residual asks for that head in a random-init evaluation; with a checkpoint that
+holds a plain controller it is an error (not with --refine_space gains either).
 """
 from __future__ import annotations
 
@@ -55,6 +58,8 @@ def main(argv=None):
                     help="report limited_rate, intervention_rate, mean_abs_delta and max_abs_action")
     ap.add_argument("--refine_coupling", choices=["joint", "local"], default="joint",
                     help="joint: the centralised filter; local: every agent refines its own action alone")
+    ap.add_argument("--ctrl_residual", action="store_true",
+                    help="random-init evaluation of a controller with the residual head (a checkpoint says it itself)")
     args = ap.parse_args(argv)
     if args.gpu is not None:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)
@@ -75,7 +80,15 @@ def main(argv=None):
         if ck_dim is not None and ck_dim != args.dim:
             ap.error(f"checkpoint {args.model_path} holds {ck_dim}-D networks (CBF input width {2 * ck_dim + 2}) "
                      f"but --dim is {args.dim}; pass --dim {ck_dim}")
-    ctrl, cbf = Controller(2 * args.dim).to(dev), CBF(2 * args.dim).to(dev)
+    residual = args.ctrl_residual
+    if args.model_path:
+        ck_res = ckpt.model_residual(args.model_path)
+        if ck_res is not None:
+            if args.ctrl_residual and not ck_res:
+                ap.error(f"--ctrl_residual contradicts checkpoint {args.model_path}, whose controller has no residual "
+                         f"head (controller_dec_net.6.weight has {2 * args.dim} rows); drop --ctrl_residual")
+            residual = ck_res
+    ctrl, cbf = Controller(2 * args.dim, residual=residual).to(dev), CBF(2 * args.dim).to(dev)
     if args.model_path:
         ckpt.load_models(args.model_path, ctrl, cbf)
     cfg = EvalConfig(num_agents=args.num_agents, num_envs=args.num_envs, seed=args.seed, refine=not args.no_refine,
@@ -95,6 +108,7 @@ def main(argv=None):
         out = evaluate(ctrl, cbf, cfg, device=dev)
     except ValueError as e:
         if not ((cfg.rollout_impl == "native" and "rollout_impl" in str(e)) or (cfg.a_max is not None and "a_max" in str(e)) or
+                (residual and "ctrl_residual" in str(e)) or
                 (cfg.refine_coupling != "joint" and "refine_coupling" in str(e))):
             raise
         ap.error(str(e))
@@ -107,6 +121,8 @@ def main(argv=None):
         out["a_max"] = cfg.a_max
     if cfg.refine_coupling != "joint":
         out["refine_coupling"] = cfg.refine_coupling
+    if residual:
+        out["ctrl_residual"] = True
     print(json.dumps(out), flush=True)
     return out
 

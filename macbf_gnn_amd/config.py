@@ -101,6 +101,10 @@ class TrainConfig:
     a_max: float = 0.0                # per-axis actuator limit of the TRAINING rollouts: the Euler step applies
                                       # clamp(a, -a_max, a_max), the backward masks dL/da (oracle.py, "Actuator
                                       # limit"); 0: off -- nothing changes by a bit. val_a_max does not follow it
+    ctrl_residual: bool = False       # controller with the residual head (oracle.py, "Residual head"): the last
+                                      # node layer has 3D rows, a_d = -(kp e_d + kv v_d) + y[2D + d], zero at the
+                                      # start; an architecture choice (a resumed checkpoint must agree); not with
+                                      # graph=True (refused by name). False: nothing changes by a bit
     # validation during training (macbf_gnn_amd/validate.py); everything is off with val_every = 0
     val_every: int = 0                # closed-loop validation every this many iterations (0: never)
     val_envs: int = 4                 # held-out scenes per rank, fixed for the whole run

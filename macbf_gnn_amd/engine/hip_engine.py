@@ -123,7 +123,8 @@ class HipEngine:
         for name, fn, width in (("cbf", L.cbf_grad_map, native.CBF_PARTIAL),
                                 ("node", node_map, native.CTRL_NODE_PARTIAL),
                                 ("edge", L.ctrl_edge_grad_map, native.CTRL_EDGE_PARTIAL)):
-            sm, dm = fn(offs, self.D)
+            # (the node maps take the last node layer's row count: 3D with the residual head)
+            sm, dm = fn(offs, self.D, self.pw.n4) if name == "node" else fn(offs, self.D)
             sm, dm = np.asarray(sm, dtype=np.int64), np.asarray(dm, dtype=np.int64)
             if sm.size and (sm.min() < 0 or sm.max() >= width or dm.min() < 0 or dm.max() >= trainer.fp.numel):
                 raise ValueError(f"gradient map {name} out of range")
@@ -387,7 +388,8 @@ class HipEngine:
             ctrl, prec, ncu = native._ctrl_fwd_kw(self.S[0], self.G, self.idx[0], pw.ctrl_w, pw.ctrl_off["ew1f"],
                                                   pw.ctrl_off["nw1f"], pw.ctrl_v, self.A[0], self.S[1], self.dist[0],
                                                   self.act[0], **self._noise_args(), pooled=self.pooled[0],
-                                                  argmax=self.argmax[0], prec=self.prec, a_max=self.a_max)
+                                                  argmax=self.argmax[0], prec=self.prec, a_max=self.a_max,
+                                                  res=self.pw.residual)
             hfwd = native._cbf_hfwd_kw(self.S, self.idx[:T], self.idx[:T], self.src, self.nev_host, pw.cbf_w,
                                        pw.cbf_off["w1f"], pw.cbf_rm, pw.cbf_v, self.hbuf, self.hmask,
                                        prec=self.prec)[0] if overlap else None
@@ -455,7 +457,8 @@ class HipEngine:
                         prev_idx=self.idx[t - 1] if t > 0 else None, sort=t % self.resort_every == 0)
             native.ctrl_fwd(self.S[t], self.G, self.idx[t], pw.ctrl_w, pw.ctrl_off["ew1f"], pw.ctrl_off["nw1f"],
                             pw.ctrl_v, self.A[t], self.S[t + 1], self.dist[t], self.act[t], noise_t=t, **self._noise_args(),
-                            pooled=self.pooled[t], argmax=self.argmax[t], prec=self.prec, a_max=self.a_max)
+                            pooled=self.pooled[t], argmax=self.argmax[t], prec=self.prec, a_max=self.a_max,
+                            res=self.pw.residual)
             if early_stop:
                 # the per-env goal distances go to pinned host memory on a side stream (the
                 # blit stays off the compute queue's critical path)
@@ -815,7 +818,7 @@ class HipEngine:
                                  self.A[:T].view(TB, N, D), self.dS[1: T + 1].view(TB, N, W), valid_u8.view(TB),
                                  pw.ctrl_rm, pw.node_rm_off, pw.ctrl_v, gs * ACT_COEF, dP[:TB], None, pn, nb_n,
                                  act_cnt=self.counts[2:3], prec=self.prec, init=True, gscale=gsd,
-                                 wrm16=self._node16(TB * N), a_max=self.a_max)
+                                 wrm16=self._node16(TB * N), a_max=self.a_max, res=self.pw.residual)
             native.ctrl_edge_bwd(self.S[:T].view(TB, Nn, W), self.idx[:T].view(TB, N, K), self.argmax[:T].view(TB, N, 128),
                                  dP[:TB], pw.ctrl_w, pw.ctrl_off["ew1f"], pw.ctrl_off["ew2tn"], None, pe, nb_e, prec=self.prec,
                                  init=True)
@@ -907,7 +910,7 @@ class HipEngine:
                 self.pooled[0], self.S[0], self.G, self.A[0], self.dS[0], self.valid_buf[0], pw.ctrl_rm, pw.node_rm_off,
                 pw.ctrl_v, 0.0, self.dP, self.ego, self.part_node[: self.nb_node], self.nb_node, act_cnt=self.counts[2:3],
                 prec=self.prec, gscale=getattr(self.tr, "gscale_dev", None), wrm16=self._node16(B * N),
-                a_max=self.a_max)
+                a_max=self.a_max, res=self.pw.residual)
             edge, _ = native._edge_bwd_kw(
                 self.S[0], self.idx[0], self.argmax[0], self.dP, pw.ctrl_w, pw.ctrl_off["ew1f"], pw.ctrl_off["ew2tn"],
                 self.dEc[0], self.part_edge[: self.nb_edge], self.nb_edge, prec=self.prec,
@@ -943,7 +946,8 @@ class HipEngine:
                         valid_t=valid_u8[t][sl], wrm=pw.ctrl_rm, offs=pw.node_rm_off, wvec=pw.ctrl_v,
                         act_coef=gs * ACT_COEF, dP=self.dP[sl], ego=self.ego[sl], partial=pn,
                         act_cnt=self.counts[2:3], prec=self.prec, init=init,
-                        gscale=getattr(self.tr, "gscale_dev", None), combine=cmb, a_max=self.a_max)
+                        gscale=getattr(self.tr, "gscale_dev", None), combine=cmb, a_max=self.a_max,
+                        res=self.pw.residual)
             edge = dict(S=self.S[t][sl], idx=self.idx[t][sl], argmax=self.argmax[t][sl], dP=self.dP[sl], wpack=pw.ctrl_w,
                         f_ew1f=pw.ctrl_off["ew1f"], f_ew2tn=pw.ctrl_off["ew2tn"], dEc=self.dEc[t & 1][sl], partial=pe,
                         prec=self.prec, init=init)

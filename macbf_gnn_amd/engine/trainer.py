@@ -67,7 +67,11 @@ class Trainer:
                 check_a_max(cfg.a_max)
             except ValueError as e:
                 raise ValueError(f"a_max must be a positive finite number, or 0 for no limit: {e}") from None
-        self.controller = Controller(2 * cfg.dim).to(self.device)
+        if cfg.ctrl_residual and cfg.graph:
+            # the captured whole-iteration graphs have not been run with the residual kernels: refused by name
+            raise ValueError("ctrl_residual has no graph mode: use graph=False (train.py: drop --graph) or "
+                             "ctrl_residual=False")
+        self.controller = Controller(2 * cfg.dim, residual=cfg.ctrl_residual).to(self.device)
         self.cbf = CBF(2 * cfg.dim).to(self.device)
         self.fp = FlatParams({"controller": self.controller, "cbf": self.cbf}, device=self.device)
         dp.broadcast_(self.fp.flat)

@@ -140,6 +140,17 @@ def check_refine_coupling(cfg: "EvalConfig") -> str:
     return c
 
 
+def check_residual(controller, cfg: "EvalConfig") -> bool:
+    """Whether ``controller`` has the residual head (``oracle.py``, "Residual head"); the option it cannot be
+    combined with is an error that names it: the gain refinement moves the gain pre-activations alone and
+    would drop the residual from the action."""
+    res = bool(getattr(controller, "residual", False))
+    if res and cfg.refine and cfg.refine_space == "gains":
+        raise ValueError("a residual controller (ctrl_residual) commands more than the gain law: refine_space='gains' "
+                         "refines the gains alone; use refine_space='actions'")
+    return res
+
+
 def check_action_limit(cfg: "EvalConfig") -> Optional[float]:
     """``cfg.a_max`` checked (``check_a_max``); the options a limit cannot be combined with are errors
     that name them."""
@@ -388,6 +399,7 @@ def rollout_eval(controller, cbf, s0, g, cfg: EvalConfig, obstacles=None) -> Dic
     if cfg.refine_impl not in ("autograd", "native"):
         raise ValueError(f"unknown refine_impl {cfg.refine_impl!r} (autograd or native)")
     check_rollout_impl(cfg, s0.device)
+    check_residual(controller, cfg)
     a_max = check_action_limit(cfg)
     coupling = check_refine_coupling(cfg)
     stats = cfg.action_stats or a_max is not None
@@ -498,6 +510,7 @@ def evaluate(controller, cbf, cfg: EvalConfig, device: Optional[torch.device] = 
     check_rollout_impl(cfg, device)
     check_action_limit(cfg)
     check_refine_coupling(cfg)
+    check_residual(controller, cfg)
     if device.type == "cuda":
         controller.mfma_dtype = cbf.mfma_dtype = MFMA_DTYPES[cfg.dtype]
     controller.eval()

@@ -2,7 +2,7 @@
 
 Used by ``models.Controller.forward`` on gfx950 (reference ``controller.py:31-63``).
 Forward: ``ctrl_fwd`` (edge MLP + masked max-pool with saved argmax slots + node MLP + gain
-law), no Euler step. Backward: ``ctrl_node_bwd`` (node MLP + gain law; the upstream dL/da is
+law, with the residual head where the module has one: ``oracle.py`` "Residual head"), no Euler step. Backward: ``ctrl_node_bwd`` (node MLP + gain law; the upstream dL/da is
 fed as the velocity adjoint of s_{t+1} = s_t + dt [v, a], i.e. G = (0, 0, dL/da / dt)),
 ``ctrl_edge_bwd`` (max-pool routing via argmax, edge MLP), ``node_combine`` (edge -> node,
 reverse CSR, no Euler term) and the slab reductions for the parameter gradients.
@@ -34,7 +34,7 @@ class _CtrlFn(torch.autograd.Function):
         pooled = torch.empty(B, N, L.pooled_row(mp.prec), dtype=w.dtype, device=dev)
         am = torch.empty(B, N, 128, dtype=torch.uint8, device=dev)
         native.ctrl_fwd(S, G, idx, w, mp.off["ew1f"], mp.off["nw1f"], v, A, None, None, None,
-                        pooled=pooled, argmax=am, prec=mp.prec)
+                        pooled=pooled, argmax=am, prec=mp.prec, res=mp.residual)
         ctx.mp = mp
         ctx.packed = (w, v, rm)
         ctx.save_for_backward(S, G, idx, A, pooled, am)
@@ -57,7 +57,8 @@ class _CtrlFn(torch.autograd.Function):
         dP = torch.empty(B, N, L.pooled_row(mp.prec), dtype=w.dtype, device=dev)
         ego = torch.empty(B, N, W, dtype=torch.float32, device=dev)
         dEc = torch.empty(B, N, K, W, dtype=torch.float32, device=dev)
-        native.ctrl_node_bwd(pooled, S, G, A, Gn, None, rm, mp.rm_off, v, 0.0, dP, ego, pn, nbn, prec=mp.prec, init=True)
+        native.ctrl_node_bwd(pooled, S, G, A, Gn, None, rm, mp.rm_off, v, 0.0, dP, ego, pn, nbn, prec=mp.prec, init=True,
+                             res=mp.residual)
         native.ctrl_edge_bwd(S, idx, am, dP, w, mp.off["ew1f"], mp.off["ew2tn"], dEc, pe, nbe, prec=mp.prec, init=True)
         gs = gg = None
         if ctx.needs_input_grad[1]:

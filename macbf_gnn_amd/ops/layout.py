@@ -194,8 +194,18 @@ def ctrl_node_slot(k: int, dim: int = 2):
     return None
 
 
-def ctrl_packer(fp_offsets: Dict[str, int], dim: int = 2) -> Packer:
-    """Fragments used by csrc/ctrl.hip."""
+def node_rows4(dim: int, n4=None) -> int:
+    """Real rows of the last node layer ``controller_dec_net.6``: 2D gain rows, or 3D with the residual
+    head (oracle.py, "Residual head"). ``n4`` None: the plain 2D. The MFMA tiles pad it to 32 (16) rows."""
+    n4 = 2 * dim if n4 is None else int(n4)
+    if n4 not in (2 * dim, 3 * dim):
+        raise ValueError(f"last node layer: {2 * dim} rows, or {3 * dim} with the residual head; got {n4}")
+    return n4
+
+
+def ctrl_packer(fp_offsets: Dict[str, int], dim: int = 2, n4=None) -> Packer:
+    """Fragments used by csrc/ctrl.hip. ``n4``: rows of the last node layer (``node_rows4``)."""
+    n4 = node_rows4(dim, n4)
     eW1, eb1 = fp_offsets["controller_centr_net.0.weight"], fp_offsets["controller_centr_net.0.bias"]
     eW2 = fp_offsets["controller_centr_net.2.weight"]
     nW1, nb1 = fp_offsets["controller_dec_net.0.weight"], fp_offsets["controller_dec_net.0.bias"]
@@ -241,8 +251,8 @@ def ctrl_packer(fp_offsets: Dict[str, int], dim: int = 2) -> Packer:
     p.add("nw1f", nw1f, 2, 9, "nat")
     p.add("nw2", _mat(nW2, 128, 64), 4, 4, "acc")
     p.add("nw3", _mat(nW3, 64, 128), 2, 8, "acc")
-    p.add("nw4", _mat(nW4, SD, 64), 1, 4, "acc")
-    p.add("nw4t", _matT(nW4, SD, 64), 2, 2, "acc")
+    p.add("nw4", _mat(nW4, n4, 64), 1, 4, "acc")
+    p.add("nw4t", _matT(nW4, n4, 64), 2, 2, "acc")
     p.add("nw3t", _matT(nW3, 64, 128), 4, 4, "acc")
     p.add("nw2t", _matT(nW2, 128, 64), 2, 8, "acc")
     p.add("nw1ft", nw1ft, 5, 4, "acc")
@@ -256,11 +266,11 @@ def cbf_vec_index(fp_offsets) -> Tuple[np.ndarray, Dict[str, int]]:
     return _vec(parts)
 
 
-def ctrl_vec_index(fp_offsets, dim: int = 2) -> Tuple[np.ndarray, Dict[str, int]]:
+def ctrl_vec_index(fp_offsets, dim: int = 2, n4=None) -> Tuple[np.ndarray, Dict[str, int]]:
     parts = [("eb2", fp_offsets["controller_centr_net.2.bias"], 128),
              ("nb2", fp_offsets["controller_dec_net.2.bias"], 128),
              ("nb3", fp_offsets["controller_dec_net.4.bias"], 64),
-             ("nb4", fp_offsets["controller_dec_net.6.bias"], 2 * dim, 32)]
+             ("nb4", fp_offsets["controller_dec_net.6.bias"], node_rows4(dim, n4), 32)]
     return _vec(parts)
 
 
@@ -354,8 +364,10 @@ class RMPacker:
 NODE_STRIDES = {"w1": 168, "w2": 68, "w3": 132, "w4": 68}
 
 
-def ctrl_node_rm(fp_offsets, dim: int = 2) -> RMPacker:
-    """Row-major node-MLP images for the controller backward kernel (csrc/ctrl.hip)."""
+def ctrl_node_rm(fp_offsets, dim: int = 2, n4=None) -> RMPacker:
+    """Row-major node-MLP images for the controller backward kernel (csrc/ctrl.hip). ``n4``: rows of the
+    last node layer (``node_rows4``)."""
+    n4 = node_rows4(dim, n4)
     nW1, nb1 = fp_offsets["controller_dec_net.0.weight"], fp_offsets["controller_dec_net.0.bias"]
     nW2 = fp_offsets["controller_dec_net.2.weight"]
     nW3 = fp_offsets["controller_dec_net.4.weight"]
@@ -372,7 +384,7 @@ def ctrl_node_rm(fp_offsets, dim: int = 2) -> RMPacker:
     p.add("w1", w1f, 64, 160, NODE_STRIDES["w1"])
     p.add("w2", _mat(nW2, 128, 64), 128, 64, NODE_STRIDES["w2"])
     p.add("w3", _mat(nW3, 64, 128), 64, 128, NODE_STRIDES["w3"])
-    p.add("w4", _mat(nW4, 2 * dim, 64), 32, 64, NODE_STRIDES["w4"])
+    p.add("w4", _mat(nW4, n4, 64), 32, 64, NODE_STRIDES["w4"])
     return p
 
 
@@ -449,7 +461,8 @@ def cbf_grad_map(fp_offsets, dim: int = 2):
     return np.asarray(S, np.int64), np.asarray(D, np.int64)
 
 
-def ctrl_node_grad_map(fp_offsets, dim: int = 2):
+def ctrl_node_grad_map(fp_offsets, dim: int = 2, n4=None):
+    n4 = node_rows4(dim, n4)
     nW1, nb1 = fp_offsets["controller_dec_net.0.weight"], fp_offsets["controller_dec_net.0.bias"]
     nW2, nb2 = fp_offsets["controller_dec_net.2.weight"], fp_offsets["controller_dec_net.2.bias"]
     nW3, nb3 = fp_offsets["controller_dec_net.4.weight"], fp_offsets["controller_dec_net.4.bias"]
@@ -464,20 +477,21 @@ def ctrl_node_grad_map(fp_offsets, dim: int = 2):
             S.append(o * 160 + k)
             D.append(nb1 + o if sl[0] == "b" else nW1 + o * n_in + sl[1])
     for s_, d_ in (_pairs_rowmajor(10240, 64, nW2, 128, 64), _pairs_rowmajor(18560, 128, nW3, 64, 128),
-                   _pairs_rowmajor(26816, 64, nW4, 2 * dim, 64)):
+                   _pairs_rowmajor(26816, 64, nW4, n4, 64)):
         S += s_; D += d_
     S += [18432 + m for m in range(128)]; D += [nb2 + m for m in range(128)]
     S += [26752 + m for m in range(64)]; D += [nb3 + m for m in range(64)]
-    S += [28864 + m for m in range(2 * dim)]; D += [nb4 + m for m in range(2 * dim)]
+    S += [28864 + m for m in range(n4)]; D += [nb4 + m for m in range(n4)]
     return np.asarray(S, np.int64), np.asarray(D, np.int64)
 
 
-def ctrl_node16_grad_map(fp_offsets, dim: int = 2):
+def ctrl_node16_grad_map(fp_offsets, dim: int = 2, n4=None):
     """Slab -> flat grad pairs of the 16x16x32 node backward (csrc/node16.h, tile-major slab):
     a 16x16 tile (M, N) is 64 lanes x 4 floats, lane l = (n = l & 15, g = l >> 4), float q ->
     row 16M + 4g + q, column 16N + n. Wave w owns dW2 tiles (w, u < 4), dW3 tiles (w & 3, 4(w >> 2) + u),
     dW1f slots v < 5 -> tile (w & 3, (w >> 2) + 2v) for tile columns < 9, dW4 tile (0, w) for w < 4;
-    then the bias rows b2 (128), b3 (64), b4 (16)."""
+    then the bias rows b2 (128), b3 (64), b4 (16). ``n4``: rows of the last node layer (``node_rows4``)."""
+    n4 = node_rows4(dim, n4)
     nW1, nb1 = fp_offsets["controller_dec_net.0.weight"], fp_offsets["controller_dec_net.0.bias"]
     nW2, nb2 = fp_offsets["controller_dec_net.2.weight"], fp_offsets["controller_dec_net.2.bias"]
     nW3, nb3 = fp_offsets["controller_dec_net.4.weight"], fp_offsets["controller_dec_net.4.bias"]
@@ -508,11 +522,11 @@ def ctrl_node16_grad_map(fp_offsets, dim: int = 2):
                     return nb1 + r if sl[0] == "b" else nW1 + r * n_in + sl[1]
                 tile((64 + w * 5 + v) * 256, w & 3, nt, w1)
         if w < 4:
-            tile((104 + w) * 256, 0, w, lambda r, c: nW4 + r * 64 + c if r < 2 * dim else None)
+            tile((104 + w) * 256, 0, w, lambda r, c: nW4 + r * 64 + c if r < n4 else None)
     b2 = 108 * 256
     S += [b2 + m for m in range(128)]; D += [nb2 + m for m in range(128)]
     S += [b2 + 128 + m for m in range(64)]; D += [nb3 + m for m in range(64)]
-    S += [b2 + 192 + m for m in range(2 * dim)]; D += [nb4 + m for m in range(2 * dim)]
+    S += [b2 + 192 + m for m in range(n4)]; D += [nb4 + m for m in range(n4)]
     return np.asarray(S, np.int64), np.asarray(D, np.int64)
 
 
@@ -585,10 +599,11 @@ def cbf_rm16(fp_offsets, dim: int = 2) -> RMPacker:
 NODE16_STRIDES = {"w1": 176, "w2": 80, "w3": 144, "w4": 80}    # csrc/node16.h N16_S1..S4 (bank model)
 
 
-def node_rm16(fp_offsets, dim: int = 2) -> RMPacker:
+def node_rm16(fp_offsets, dim: int = 2, n4=None) -> RMPacker:
     """Row-major node-MLP images for the 16x16x32 x3 node backward (csrc/node16.h): W1f (64 x 160,
     the layer-1 slots of ctrl_node_slot in natural order: its forward B operand is the pooled row),
-    W2 (128x64), W3 (64x128) and W4 (16 x 64: rows >= 2D zero), the last three column-permuted
+    W2 (128x64), W3 (64x128) and W4 (16 x 64: rows past the layer's ``n4`` real ones zero, ``node_rows4``),
+    the last three column-permuted
     (perm32_logical: their forward B operands are packed C-tile pairs). A = W is one 16-byte read
     per lane, A = W^T two ds_read_b64_tr_b16."""
     nW1, nb1 = fp_offsets["controller_dec_net.0.weight"], fp_offsets["controller_dec_net.0.bias"]
@@ -596,6 +611,7 @@ def node_rm16(fp_offsets, dim: int = 2) -> RMPacker:
     nW3 = fp_offsets["controller_dec_net.4.weight"]
     nW4 = fp_offsets["controller_dec_net.6.weight"]
     n_in = 128 + 2 * dim
+    n4 = node_rows4(dim, n4)
 
     def w1f(o, k):
         sl = ctrl_node_slot(k, dim)
@@ -603,12 +619,12 @@ def node_rm16(fp_offsets, dim: int = 2) -> RMPacker:
             return ZERO
         return nb1 + o if sl[0] == "b" else nW1 + o * n_in + sl[1]
 
-    m2, m3, m4 = _mat(nW2, 128, 64), _mat(nW3, 64, 128), _mat(nW4, 2 * dim, 64)
+    m2, m3, m4 = _mat(nW2, 128, 64), _mat(nW3, 64, 128), _mat(nW4, n4, 64)
     p = RMPacker()
     p.add("w1", w1f, 64, 160, NODE16_STRIDES["w1"])
     p.add("w2", lambda r, c: m2(r, perm32_logical(c)), 128, 64, NODE16_STRIDES["w2"])
     p.add("w3", lambda r, c: m3(r, perm32_logical(c)), 64, 128, NODE16_STRIDES["w3"])
-    p.add("w4", lambda r, c: m4(r, perm32_logical(c)) if r < 2 * dim else ZERO, 16, 64, NODE16_STRIDES["w4"])
+    p.add("w4", lambda r, c: m4(r, perm32_logical(c)) if r < n4 else ZERO, 16, 64, NODE16_STRIDES["w4"])
     return p
 
 

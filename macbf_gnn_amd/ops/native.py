@@ -372,10 +372,12 @@ def _records(t, name, lead, W, min_rows=None):
 
 
 def _ctrl_fwd_kw(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise=None, pooled=None, argmax=None,
-                 prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None, a_max=None):
+                 prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None, a_max=None, res=False):
     """ctrl_fwd's checks -> (the CtrlArgs fields (csrc/args.h) as a dict, precision code, num_cu).
     a_max (optional): the training rollout's per-axis actuator limit (oracle.py, "Actuator limit"); the
-    key is only there with a limit, so a call without one passes what it always passed."""
+    key is only there with a limit, so a call without one passes what it always passed. res: the packed
+    controller has the residual head (oracle.py, "Residual head": 3D rows in the last node layer, what
+    ``PackedWeights.residual`` / ``ModulePack.residual`` say); the key is only there with it."""
     B, N, K = idx.shape
     D = dim_of(S)
     W = rec_width(D)
@@ -426,18 +428,23 @@ def _ctrl_fwd_kw(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_su
               noise_t=int(noise_t), stamps=ptr(stamps))
     if _a_max(a_max) > 0.0:
         kw["a_max"] = _a_max(a_max)
+    if res:
+        if stamps is not None:
+            raise NativeError("ctrl_fwd stamps: the residual kernels have no phase clocks")
+        kw["res"] = 1
     return kw, f16, num_cu(S.device)
 
 
 def ctrl_fwd(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise=None, pooled=None, argmax=None,
-             prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None, a_max=None):
+             prec=None, noise_key=None, noise_prob=0.0, noise_scale=0.0, noise_t=0, stamps=None, a_max=None, res=False):
     """Fused controller step on per-step views: S/Sn (B,Nn,W) node records (agents first),
     G (B,N,D), idx (B,N,K), A (B,N,D), dist_sum/act_sum (B,) int64 fixed point (x FX_DIST /
     x FX_ACT: order-independent integer atomics), pooled (B,N,128) bf16
     ((B,N,256) [hi | lo] rows for prec="fp32", required there), argmax (B,N,128) uint8.
-    a_max (optional): Sn applies clamp(a, -a_max, a_max); A and act_sum keep the raw action."""
+    a_max (optional): Sn applies clamp(a, -a_max, a_max); A and act_sum keep the raw action.
+    res: the packed controller has the residual head (a_q += y4[2D + q])."""
     kw, f16, ncu = _ctrl_fwd_kw(S, G, idx, wpack, f_edge, f_node, wvec, A, Sn, dist_sum, act_sum, noise, pooled, argmax,
-                                prec, noise_key, noise_prob, noise_scale, noise_t, stamps, a_max)
+                                prec, noise_key, noise_prob, noise_scale, noise_t, stamps, a_max, res)
     _ok(lib().ctrl_fwd(num_cu=ncu, prec=f16, stream=stream_handle(), **kw), "ctrl_fwd")
 
 
@@ -1162,9 +1169,10 @@ NODE16_RM = 64 * 176 + 128 * 80 + 64 * 144 + 16 * 80    # csrc/node16.h: element
 
 def _node_bwd_kw(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
                  act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, wrm16=None,
-                 a_max=None):
+                 a_max=None, res=False):
     """ctrl_node_bwd's checks -> (the CtrlNodeBwdArgs fields (csrc/args.h) as a dict, precision code).
-    a_max (optional): the rollout's actuator limit -- the key is only there with a limit."""
+    a_max (optional): the rollout's actuator limit -- the key is only there with a limit. res: the packed
+    controller has the residual head -- the key is only there with it."""
     B, N = G.shape[:2]
     D = dim_of(S)
     W = rec_width(D)
@@ -1219,21 +1227,26 @@ def _node_bwd_kw(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, eg
         kw["wrm16"] = ptr(wrm16)
     if _a_max(a_max) > 0.0:
         kw["a_max"] = _a_max(a_max)
+    if res:
+        if stamps is not None:
+            raise NativeError("ctrl_node_bwd stamps: the residual kernels have no phase clocks")
+        kw["res"] = 1
     return kw, f16
 
 
 def ctrl_node_bwd(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
                   act_cnt=None, prec=None, init=False, chunk=None, gscale=None, combine=None, stamps=None, wrm16=None,
-                  a_max=None):
+                  a_max=None, res=False):
     """act_cnt: optional 1-element device tensor holding the (all-reduced) action-loss count
     n_act; the action-loss coefficient is then act_coef / max(n_act, 1), read by the kernel (no
     host round trip, no extra launch). init: write the weight-gradient slabs instead of
     accumulating into them (no zero fill needed). stamps: diagnostics only, int64
     (num_blocks, 4, 16) phase clocks of the cooperative 32-agent path (scripts/stamps_node.py).
     a_max (optional): the rollout's actuator limit -- dL/da through the Euler step is zero where the
-    raw action A lies outside [-a_max, a_max] or is NaN (the action-loss term is kept)."""
+    raw action A lies outside [-a_max, a_max] or is NaN (the action-loss term is kept).
+    res: the packed controller has the residual head (dL/dy4[2D + q] = da_q)."""
     kw, f16 = _node_bwd_kw(pooled, S, G, A, Gn, valid_t, wrm, offs, wvec, act_coef, dP, ego, partial, num_blocks,
-                           act_cnt, prec, init, chunk, gscale, combine, stamps, wrm16, a_max)
+                           act_cnt, prec, init, chunk, gscale, combine, stamps, wrm16, a_max, res)
     _ok(lib().ctrl_node_bwd(num_blocks=int(num_blocks), prec=f16, stream=stream_handle(), **kw), "ctrl_node_bwd")
 
 
@@ -1758,7 +1771,7 @@ def episode_run(buf: dict, *, K, max_steps, check_every, refine, loops, lr, mask
     cs, sc = _scan_kw(S0, g("idx"), None, None, g("safe"), K=K, perm=g("perm"), n_agents=N)
     _, fin = _scan_kw(S0, None, None, None, g("safe"), K=1, do_knn=False, perm=g("perm"), n_agents=N)
     ck, pc, ncu = _ctrl_fwd_kw(S0, g("G"), g("idx"), cw, cmp_.off["ew1f"], cmp_.off["nw1f"], cv, g("A"), None, None, None,
-                               pooled=g("pooled"), argmax=g("argmax"), prec=cmp_.prec)
+                               pooled=g("pooled"), argmax=g("argmax"), prec=cmp_.prec, res=cmp_.residual)
     cbf_kw, nb = None, 0
     if filt:
         cbf_kw, _, nb = _cbf_fwd_kw(S0[None], g("idx")[None], bw, bmp.off["w1f"], bv, two=False, h_out=g("h")[None],

@@ -49,6 +49,7 @@ class ModulePack:
         offs, self.shapes, self.n = _offsets(module)
         dim = module.in_dim // 2
         self.dim = dim
+        self.residual = False
         mk = lambda a: torch.as_tensor(L.resolve(a, self.n), dtype=torch.long, device=device)
         mkl = lambda a: torch.as_tensor(a, dtype=torch.long, device=device)
         if kind == "cbf":
@@ -57,10 +58,13 @@ class ModulePack:
             rm = L.cbf_rm(offs)
             self.maps = {"cbf": tuple(mkl(x) for x in L.cbf_grad_map(offs, dim))}
         elif kind == "ctrl":
-            pk = L.ctrl_packer(offs, dim)
-            vec, _ = L.ctrl_vec_index(offs, dim)
-            rm = L.ctrl_node_rm(offs, dim)
-            self.maps = {"node": tuple(mkl(x) for x in L.ctrl_node_grad_map(offs, dim)),
+            # rows of the last node layer: 2D, or 3D with the residual head (oracle.py, "Residual head")
+            n4 = int(dict(module.named_parameters())["controller_dec_net.6.weight"].shape[0])
+            self.residual = n4 == 3 * dim
+            pk = L.ctrl_packer(offs, dim, n4)
+            vec, _ = L.ctrl_vec_index(offs, dim, n4)
+            rm = L.ctrl_node_rm(offs, dim, n4)
+            self.maps = {"node": tuple(mkl(x) for x in L.ctrl_node_grad_map(offs, dim, n4)),
                          "edge": tuple(mkl(x) for x in L.ctrl_edge_grad_map(offs, dim))}
         else:
             raise ValueError(kind)
@@ -94,7 +98,7 @@ def module_pack(kind: str, module, device, dtype=None) -> ModulePack:
     reference precision, fp32-accurate x3 kernels), torch.bfloat16 or torch.float16 (one 16-bit
     MFMA per product)."""
     dtype = dtype or getattr(module, "mfma_dtype", torch.float32)
-    key = (kind, module.in_dim, str(device), dtype)
+    key = (kind, module.in_dim, str(device), dtype, bool(getattr(module, "residual", False)))
     mp = _CACHE.get(key)
     if mp is None:
         mp = ModulePack(kind, module, device, dtype)

@@ -169,7 +169,8 @@ def edge_oracle(p, S, idx, argmax, dP, N, D):
 def node_oracle(p, pooled_hi, pooled_lo, S, G, A, Gn, valid, c, a_max=None):
     """float64 autograd of ONE controller node-backward call (csrc/node16.h, csrc/ctrl.hip
     node_bwd_body / node_bwd_coop / ctrl_bwd_step). Per agent, ex = p - g, x = [pooled, ex, v],
-    y = dec_net(x), k = 2 sigmoid(y) + 0.2, a_q = -(k_2q ex_q + k_2q+1 v_q), a_ref = -(ex + sqrt3 v):
+    y = dec_net(x), k = 2 sigmoid(y) + 0.2, a_q = -(k_2q ex_q + k_2q+1 v_q) (+ y_{2D+q} where the last layer has
+    3D rows: the residual head), a_ref = -(ex + sqrt3 v):
 
         L = sum_agents dt sum_q Gn_v[q] m_q a_q + c valid_b | |A^|^2 - |a_ref|^2 |
 
@@ -206,9 +207,11 @@ def node_oracle(p, pooled_hi, pooled_lo, S, G, A, Gn, valid, c, a_max=None):
         if li != 6:
             tie |= _tie(pre.detach(), z.detach(), w.detach(), b.detach())
             z = F.relu(pre)
-    k = 2.0 * torch.sigmoid(pres[-1]) + 0.2
+    k = 2.0 * torch.sigmoid(pres[-1][:, :2 * D]) + 0.2
     kp, kv = k[:, 0::2], k[:, 1::2]
     a = -(kp * ex + kv * v)
+    if pres[-1].shape[-1] == 3 * D:       # residual head (oracle.py): a_q += y[2D + q], from the parameter shape
+        a = a + pres[-1][:, 2 * D:]
     ar = -(ex + C.SQRT3 * v)
     m = torch.ones_like(Af) if not a_max else ((Af >= -a_max) & (Af <= a_max)).double()
     ah = a + (Af - a).detach()
@@ -380,10 +383,10 @@ def _node_check(engine, gen, B=2, N=256) -> dict:
         ego = torch.zeros(B, N, W, dtype=torch.float32, device=dev)
         part = torch.zeros(nb, native.CTRL_NODE_PARTIAL, dtype=torch.float32, device=dev)
         native.ctrl_node_bwd(pooled, S, G, A, Gn, valid, pw.ctrl_rm, pw.node_rm_off, pw.ctrl_v, 0.37, dP, ego, part, nb,
-                             act_cnt=act_cnt, prec=pw.prec, init=True, chunk=128, wrm16=wrm16)
+                             act_cnt=act_cnt, prec=pw.prec, init=True, chunk=128, wrm16=wrm16, res=pw.residual)
         torch.cuda.synchronize(dev)
         red = part.double().sum(0)
-        sm, dm = gmap(offs, D)
+        sm, dm = gmap(offs, D, pw.n4)
         g = torch.zeros(engine.tr.fp.numel, dtype=torch.float64, device=dev)
         g.index_add_(0, torch.as_tensor(dm, device=dev), red[torch.as_tensor(sm, device=dev)])
         dPf = dP[..., :128].double() + (dP[..., 128:].double() if prow == 256 else 0.0)

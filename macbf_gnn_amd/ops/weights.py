@@ -22,13 +22,16 @@ class PackedWeights:
         offs = {pn: o for (m, pn, shape, o, n) in fp.specs}
         dev = fp.flat.device
         n = fp.numel
-        self.ctrl_pk = L.ctrl_packer(offs, dim)
+        # rows of the last node layer: 2D, or 3D with the residual head (oracle.py, "Residual head")
+        self.n4 = n4 = next(int(shape[0]) for (m, pn, shape, o, k) in fp.specs if pn == "controller_dec_net.6.weight")
+        self.residual = n4 == 3 * dim
+        self.ctrl_pk = L.ctrl_packer(offs, dim, n4)
         self.cbf_pk = L.cbf_packer(offs, dim)
         self.ctrl_off = self.ctrl_pk.offsets()
         self.cbf_off = self.cbf_pk.offsets()
-        cv, self.ctrl_voff = L.ctrl_vec_index(offs, dim)
+        cv, self.ctrl_voff = L.ctrl_vec_index(offs, dim, n4)
         bv, self.cbf_voff = L.cbf_vec_index(offs)
-        self.node_rm = L.ctrl_node_rm(offs, dim)
+        self.node_rm = L.ctrl_node_rm(offs, dim, n4)
         self.node_rm_off = self.node_rm.offsets()
         self.cbf_rmp = L.cbf_rm(offs)
         # all 16-bit buffers are views of one allocation (segments 256-element aligned), the
@@ -43,7 +46,7 @@ class PackedWeights:
         self.cbf_rmp16 = L.cbf_rm16(offs)
         self.cbf_pk16 = L.cbf_packer16(offs, dim)
         self.ctrl_pk16 = L.ctrl_edge_packer16(offs, dim)
-        self.node_rmp16 = L.node_rm16(offs, dim)
+        self.node_rmp16 = L.node_rm16(offs, dim, n4)
         seg16 += [planes(L.resolve(self.cbf_rmp16.index(), n)),
                   frags(L.resolve(self.cbf_pk16.index(), n)),
                   frags(L.resolve(self.ctrl_pk16.index(), n)),

@@ -44,6 +44,28 @@ native argument structs 0 means off. Per rollout step and action component q::
   for h'.
 * With the limit off nothing changes by a bit.
 
+Residual head (``Controller(in_dim, residual=True)``, ``TrainConfig.ctrl_residual``, ``train.py
+--ctrl_residual``; opt-in). The one statement of the controller's additive acceleration term; the
+kernels (``csrc/ctrl.hip`` ``node_phase`` and the node-backward prologues, ``csrc/node16.h``) and
+``docs/ARCHITECTURE.md`` point here. The gain law alone scales each axis' approach to the goal and
+cannot push sideways; with the residual the last layer ``controller_dec_net.6`` is ``Linear(64, 3D)``
+instead of ``Linear(64, 2D)`` (same parameter names, only that layer's shape differs), and for the
+layer's output y and action component q::
+
+    r_q  = y[2D + q]                          rows 0..2D-1 stay the gain pre-activations
+    a_q  = -(kp_q e_q + kv_q v_q) + r_q       then exploration noise, then the clamp, as without it
+    dL/dy[2D + q] = da_q                      the same da the gain rows use: after the clamp's mask
+                                              and after the action-loss term; e and v get nothing
+                                              from the residual
+
+* The residual is linear: no bound, no new constant. The action regulariser sees the full action and
+  ``a_max`` clamps it where the user sets one.
+* The residual rows (weight and bias) start at zero: a fresh residual controller commands the gain
+  law's actions. Every other row and layer is initialised as ``nn.Linear`` does.
+* Everything here works from the row count of ``controller_dec_net.6.weight``; no flag is passed.
+* Graph mode (``TrainConfig.graph``, ``train.py --graph``) is refused with it by name.
+* Without the residual nothing changes by a bit.
+
 Reference cites: kNN ``core.py:234-250``; controller ``controller.py:31-63``; CBF
 ``cbf.py:21-45``; TTC ``core.py:187-231``; losses ``core.py:89-184``; loop ``train.py:48-105``.
 """
@@ -173,26 +195,32 @@ def safe_agent_count(s: torch.Tensor, nodes: Optional[torch.Tensor] = None) -> t
 # inputs are exact (hi/lo split along k, csrc/common.h mma_bx) and accumulation is fp32.
 # With the weights rounded to bf16 as well, the oracle then evaluates the kernels' function up
 # to accumulation order and rounding-boundary ties.
-_EMULATE = {"bf16": False}
+_EMULATE = {"bf16": False, "dtype": torch.bfloat16}
 
 
 class emulate_bf16:
-    """Context manager: oracle networks round like the bf16 kernels (see above)."""
+    """Context manager: oracle networks round like the bf16 kernels (see above). ``dtype=torch.float16``:
+    like the fp16 build, which rounds at the same points to the other 16-bit type -- the name is the
+    older one and says bf16 either way. Only tests/test_gpu_ctrl_residual_bwd.py uses the fp16 mode (at
+    2e-2 per tensor); the plain controller's fp16 tests still compare with the non-emulating float64 oracle
+    by the looser rule of tests/test_gpu_fp16.py, so the two compare the same kernels by different rules."""
 
-    def __init__(self, on: bool = True):
+    def __init__(self, on: bool = True, dtype=torch.bfloat16):
         self.on = on
+        self.dtype = dtype
 
     def __enter__(self):
-        self.prev = _EMULATE["bf16"]
+        self.prev = dict(_EMULATE)
         _EMULATE["bf16"] = self.on
+        _EMULATE["dtype"] = self.dtype
         return self
 
     def __exit__(self, *exc):
-        _EMULATE["bf16"] = self.prev
+        _EMULATE.update(self.prev)
 
 
 def _round16(x):
-    return x.to(torch.bfloat16).to(x.dtype)
+    return x.to(_EMULATE["dtype"]).to(x.dtype)
 
 
 class _RoundFwd(torch.autograd.Function):        # activation rounding, straight-through grad
@@ -254,7 +282,8 @@ def controller_forward(p: Dict[str, torch.Tensor], s, g, idx, return_aux=False, 
 
     ``p`` is the controller ``state_dict`` (or named parameters) keyed like the reference.
     D-dimensional: edge input [s_i - s_j, eye] (2D+1), node input [pooled, p - g, v] (128+2D),
-    2D gains, a_d = -(k_{2d} (p_d - g_d) + k_{2d+1} v_d) (D = 2: the reference law).
+    2D gains, a_d = -(k_{2d} (p_d - g_d) + k_{2d+1} v_d) (D = 2: the reference law); a last layer of
+    3D rows adds the residual a_d += y[2D + d] (module docstring, "Residual head").
     ``pool_slots`` (..., N, 128; 255 = no positive row) replaces the max-pool's argmax by given
     neighbour slots (the kernels' saved argmax): the max-pool subgradient at near-ties is a
     choice, and tests pin it to the kernels' choice (see ``pool_slot_gap``). ``pool_values``
@@ -283,9 +312,11 @@ def controller_forward(p: Dict[str, torch.Tensor], s, g, idx, return_aux=False, 
         z = _lin(z, p[f"controller_dec_net.{i}.weight"], p[f"controller_dec_net.{i}.bias"], first=i == 0)
         if act:
             z = F.relu(z)
-    k = 2.0 * torch.sigmoid(z) + 0.2
+    k = 2.0 * torch.sigmoid(z[..., :2 * D]) + 0.2
     a = torch.stack([-(k[..., 2 * q] * (s[..., q] - g[..., q]) + k[..., 2 * q + 1] * s[..., D + q])
                      for q in range(D)], dim=-1)
+    if z.shape[-1] == 3 * D:          # residual head (module docstring): rows 2D..3D-1 add to the action
+        a = a + z[..., 2 * D:]
     if return_aux:
         return a, {"gains": k, "pooled": pooled, "mask": mask, "hm": hm}
     return a

@@ -43,13 +43,17 @@ def save(trainer, path: str):
 
 
 # architecture-defining config entries a resumed checkpoint must agree on
-ARCH_KEYS = ("dim", "top_k", "num_obstacles", "obstacle_points")
+# (a checkpoint from before ctrl_residual existed holds a plain controller: its missing key reads False)
+ARCH_KEYS = ("dim", "top_k", "num_obstacles", "obstacle_points", "ctrl_residual")
+ARCH_DEFAULTS = {"ctrl_residual": False}
 
 
 def load(trainer, path: str, strict: bool = True):
     ck = torch.load(path, map_location="cpu", weights_only=True)
     saved = ck.get("config") if isinstance(ck.get("config"), dict) else {}
     for k in ARCH_KEYS:
+        if saved and k not in saved and k in ARCH_DEFAULTS:
+            saved = dict(saved, **{k: ARCH_DEFAULTS[k]})
         if k in saved and hasattr(trainer.cfg, k) and saved[k] != getattr(trainer.cfg, k):
             raise ValueError(f"checkpoint {path} was written with {k}={saved[k]!r}, "
                              f"the current run has {k}={getattr(trainer.cfg, k)!r}")
@@ -127,4 +131,20 @@ def model_dim(path: str):
             return (int(sd["cbf_net.0.weight"].shape[1]) - 2) // 2
         if "controller_centr_net.0.weight" in sd:
             return (int(sd["controller_centr_net.0.weight"].shape[1]) - 1) // 2
+    return None
+
+
+def model_residual(path: str):
+    """Whether the controller in a checkpoint has the residual head (``oracle.py``, "Residual head"), from the
+    row count of its last node layer ``controller_dec_net.6.weight`` (3D with it, 2D without; D from the
+    layer's own network: the edge net's input is 2D + 1 wide), or None when the file holds no controller."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    for sd in (ck.get("controller"), ck):
+        if isinstance(sd, dict) and "controller_dec_net.6.weight" in sd and "controller_centr_net.0.weight" in sd:
+            D = (int(sd["controller_centr_net.0.weight"].shape[1]) - 1) // 2
+            rows = int(sd["controller_dec_net.6.weight"].shape[0])
+            if rows not in (2 * D, 3 * D):
+                raise ValueError(f"checkpoint {path}: controller_dec_net.6.weight has {rows} rows, expected {2 * D} "
+                                 f"or {3 * D} (residual head) for {D}-D networks")
+            return rows == 3 * D
     return None

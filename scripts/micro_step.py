@@ -77,13 +77,13 @@ def k_scan_safeonly():
 def k_fwd():
     native.ctrl_fwd(eng.S[t], eng.G, eng.idx[t], pw.ctrl_w, pw.ctrl_off["ew1f"], pw.ctrl_off["nw1f"], pw.ctrl_v,
                     eng.A[t], eng.S[t + 1], eng.dist[t], eng.act[t], pooled=eng.pooled[t], argmax=eng.argmax[t],
-                    prec=eng.prec)
+                    prec=eng.prec, res=pw.residual)
 
 
 def k_node():
     native.ctrl_node_bwd(eng.pooled[t], eng.S[t], eng.G, eng.A[t], eng.Gb[t + 1], valid, pw.ctrl_rm,
                          pw.node_rm_off, pw.ctrl_v, 1.0, eng.dP, eng.ego, eng.part_node, eng.nb_node,
-                         act_cnt=eng.counts[2:3], prec=eng.prec)
+                         act_cnt=eng.counts[2:3], prec=eng.prec, res=pw.residual)
 
 
 def k_edge():

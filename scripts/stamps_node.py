@@ -52,7 +52,8 @@ def main():
         native.ctrl_node_bwd(eng.pooled[t], eng.S[t], eng.G, eng.A[t], eng.Gb[t + 1], valid, pw.ctrl_rm,
                              pw.node_rm_off, pw.ctrl_v, 1.0, eng.dP, eng.ego, part, nb,
                              act_cnt=eng.counts[2:3], prec=eng.prec, stamps=st, chunk=128 if a.node16 else 32,
-                             wrm16=pw.node_rm16 if a.node16 else None)
+                             wrm16=pw.node_rm16 if a.node16 else None,
+                             res=pw.residual)      # (a residual engine is refused by name: no phase clocks)
         torch.cuda.synchronize()
     s = st.cpu()
     used = s[:, 0, 0] > 0

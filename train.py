@@ -9,7 +9,9 @@ each rank trains ``--num_envs`` environments and gradients are all-reduced over 
 JSON line, with and without the CBF safety filter); ``--save_best`` keeps ``<model_path>.best``;
 ``--val_a_max A`` validates under the actuator limit |u| <= A per axis; ``--a_max A`` trains under it
 (the rollout applies the clamped action, the backward masks the saturated components; the log lines
-gain ``limited_rate``). Neither option follows the other. ``--val_refine_coupling local`` validates with
+gain ``limited_rate``). Neither option follows the other. ``--ctrl_residual`` gives the controller the
+residual head: an additive acceleration beside the gain law, which starts at zero (an architecture
+choice: a resumed checkpoint must agree; not with ``--graph``). ``--val_refine_coupling local`` validates with
 the decentralised filter (every agent refines its own action alone).
 """
 from __future__ import annotations
@@ -63,6 +65,9 @@ def parse_args(argv=None):
     p.add_argument("--a_max", type=float, default=0.0,
                    help="per-axis actuator limit |u| <= this on the TRAINING rollouts (0: off): clamp in the rollout, "
                         "mask in the backward; adds limited_rate to the log lines. --val_a_max is set separately")
+    p.add_argument("--ctrl_residual", action="store_true",
+                   help="controller with the residual head: the last node layer has 3D rows, a_d = -(kp e + kv v) + r_d "
+                        "(zero at the start); combines with --a_max, not with --graph")
     p.add_argument("--save_best", action="store_true",
                    help="keep <model_path>.best at the best validation value of --best_metric")
     p.add_argument("--best_metric", type=str, default="",
@@ -72,6 +77,8 @@ def parse_args(argv=None):
 
 def build_config(args):
     from macbf_gnn_amd import config as C
+    if args.ctrl_residual and args.graph:
+        raise SystemExit("train.py: --ctrl_residual has no graph mode; drop --graph or --ctrl_residual")
     cfg = C.TrainConfig(num_agents=args.num_agents, num_envs=args.num_envs, seed=args.seed,
                         device=args.device, dtype=args.dtype, bptt=not args.no_bptt,
                         reuse_nbr_idx=not args.no_reuse_nbr_idx,
@@ -80,7 +87,7 @@ def build_config(args):
                         num_obstacles=args.num_obstacles, graph=args.graph, val_every=args.val_every,
                         val_refine=not args.no_val_refine, save_best=args.save_best, best_metric=args.best_metric,
                         val_impl=args.val_impl, val_a_max=args.val_a_max, a_max=args.a_max,
-                        val_refine_coupling=args.val_refine_coupling)
+                        val_refine_coupling=args.val_refine_coupling, ctrl_residual=args.ctrl_residual)
     for name in ("train_steps", "inner_loops", "top_k", "lr", "display_steps", "save_steps", "val_envs",
                  "val_refine_loops"):
         v = getattr(args, name)
