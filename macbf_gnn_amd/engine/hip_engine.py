@@ -20,6 +20,8 @@ backward
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 
 import torch
@@ -37,6 +39,22 @@ ACT_COEF = C.LOSS_SCALE * C.LOSS_WEIGHTS[4]
 STEP_ROWS_BYTES = 64 << 20      # per-step slab rows for BPTT grids whose T x rows fit this (HipEngine.step_rows)
 STATS_COLS = 18       # StepStats row: 10 loss sums | 3 counts | 3 local | skipped | loss scale
 STATS_RING = 256
+
+
+@contextlib.contextmanager
+def _capture_gc_guard():
+    """Graph captures run with the cyclic collector off, after one collection: a dead engine in a
+    reference cycle still owns its captured graphs, and collecting it inside a capture destroys HIP
+    graph objects, which HIP refuses while a stream is capturing -- the destructor's error then
+    terminates the process (torch.cuda.graph no longer collects before it begins)."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 class HipEngine:
@@ -609,7 +627,7 @@ class HipEngine:
         dirty = self._sums_dirty
         self._bwd_capture = True
         try:
-            with torch.cuda.graph(g, pool=self._bwd_pool, stream=side):
+            with _capture_gc_guard(), torch.cuda.graph(g, pool=self._bwd_pool, stream=side):
                 valid = self._counts(T)
                 self._backward(T, valid)
         finally:
@@ -659,10 +677,10 @@ class HipEngine:
             cur.wait_stream(side)
             pool = torch.cuda.graph_pool_handle()
             ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ga, pool=pool):
+            with _capture_gc_guard(), torch.cuda.graph(ga, pool=pool):
                 self._rollout_steps(False)
                 self._graph_valid = self._counts(T)
-            with torch.cuda.graph(gb, pool=pool):
+            with _capture_gc_guard(), torch.cuda.graph(gb, pool=pool):
                 self._graph_stats = self._backward(T, self._graph_valid)
             self._graphs = (ga, gb)
         finally:

@@ -130,10 +130,12 @@ def edge_forward(p, S, idx, N, D):
     return rel, eye, il, ar
 
 
-def edge_oracle(p, S, idx, argmax, dP, N, D):
+def edge_oracle(p, S, idx, argmax, dP, N, D, exact=None):
     """float64: dL/d(s_i - s_j) (B, N, K, 2D), tie flags (B, N, K), dW dict, |term| scales, row
     scales, for L = sum dP * maxpool_{argmax}(mask * relu(W2 relu(W1 [rel, eye] + b1) + b2)); the
-    max-pool is routed through the given argmax slots (the kernel's saved ones)."""
+    max-pool is routed through the given argmax slots (the kernel's saved ones). dP rows: 256 wide
+    [hi | lo] (x3) or 128 wide (one 16-bit plane). exact (B, N, K) bool: edges whose radius test is
+    exact in fp32 and float64 alike (planted on a grid): they get no radius-tie flag."""
     B, _, K = idx.shape
     rel, eye, il, ar = edge_forward(p, S, idx, N, D)
     pr = {n_: v.clone().requires_grad_(True) for n_, v in p.items() if n_.startswith("controller_centr_net")}
@@ -141,6 +143,8 @@ def edge_oracle(p, S, idx, argmax, dP, N, D):
     d = torch.sqrt((rel[..., :D] ** 2).sum(-1))
     mask = (d < C.OBS_RADIUS).double()
     tie = ((d - C.OBS_RADIUS).abs() <= 1e-6).reshape(-1)
+    if exact is not None:
+        tie = tie & ~exact.reshape(-1).to(tie.device)
     w1, b1 = pr["controller_centr_net.0.weight"], pr["controller_centr_net.0.bias"]
     w2, b2 = pr["controller_centr_net.2.weight"], pr["controller_centr_net.2.bias"]
     x = x.reshape(-1, x.shape[-1])
@@ -153,7 +157,9 @@ def edge_oracle(p, S, idx, argmax, dP, N, D):
     sl = argmax.long()
     has = (sl < K).double()
     pooled = hm.gather(-2, sl.clamp(max=K - 1).unsqueeze(-2)).squeeze(-2) * has
-    dPf = dP[..., :128].double() + dP[..., 128:256].double()          # x3 rows: [hi | lo]
+    dPf = dP[..., :128].double()
+    if dP.shape[-1] >= 256:
+        dPf = dPf + dP[..., 128:256].double()                          # x3 rows: [hi | lo]
     grads = torch.autograd.grad((dPf * pooled).sum(), [rel] + list(pr.values()) + [z1, z2])
     notself = (il != ar).double().unsqueeze(-1)
     drel = grads[0] * notself                             # self pairs: +i - i cancels, the kernel writes 0

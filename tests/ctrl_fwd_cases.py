@@ -63,11 +63,30 @@ def controller(D, seed=0):
 
 @functools.lru_cache(maxsize=None)
 def build(name):
-    """-> dict of CPU tensors (shared between tests: treat as read-only): s (B, Nn, 2D) node states
-    (agents first, obstacle points after with zero velocity), G (B, N, D), idx (B, N, K) int32, and
-    the plants: per env the agent indices P, Q, T, R1 < R2 and `rest`; planted (B, N, K) bool = the
-    edges whose radius mask is planted and exact."""
-    c = dict(CASES[name])
+    """The shared case `name` of CASES, built once (see _from_spec)."""
+    return _from_spec(name, CASES[name])
+
+
+_SPEC_BUILT = {}
+
+
+def build_spec(name, spec):
+    """A case from a spec dict in the form of CASES' entries, built once per (name, spec); a name of
+    CASES with that entry's spec is build(name) itself."""
+    if CASES.get(name) == spec:
+        return build(name)
+    key = (name, tuple(sorted(spec.items())))
+    if key not in _SPEC_BUILT:
+        _SPEC_BUILT[key] = _from_spec(name, spec)
+    return _SPEC_BUILT[key]
+
+
+def _from_spec(name, spec):
+    """spec: dict(D, B, N, K, nobs, dens, seed) -> dict of CPU tensors (shared between tests: treat
+    as read-only): s (B, Nn, 2D) node states (agents first, obstacle points after with zero
+    velocity), G (B, N, D), idx (B, N, K) int32, and the plants: per env the agent indices P, Q, T,
+    R1 < R2 and `rest`; planted (B, N, K) bool = the edges whose radius mask is planted and exact."""
+    c = dict(spec)
     D, B, N, K, nobs = c["D"], c["B"], c["N"], c["K"], c["nobs"]
     gen = torch.Generator().manual_seed(7000 + c["seed"])
     plants = N >= 5 and K >= 2                 # (K = 1 lists the self edge only: nothing to plant)

@@ -225,3 +225,83 @@ def make_case(T, B, N, K, seed, recomputed, valid_pattern):
 
 def case_seed(shape):
     return 11 + SHAPES.index(tuple(shape))
+
+
+# ------------------------------------------------------------------------- cbf_match on planted lists
+def match_reference_fast(idx, T, recomputed=False):
+    """ops.dedup.match_reference without a Python loop over slots (broadcast compares, one cumulative
+    sum for the extras' ranks): the same (map1 (T, B, N, K), src (2E,), nev) as int64 tensors.
+    tests/test_dedup.py pins it to the loop reference on every small case."""
+    _, B, N, K = idx.shape
+    BNK = B * N * K
+    E = T * BNK
+    idx = idx.long().cpu()
+    m = torch.full((T, B, N, K), -1, dtype=torch.long)
+    if T > 1:
+        if recomputed:
+            m[:T - 1] = torch.arange(K)
+        else:
+            eq = idx[:T - 1].unsqueeze(-1) == idx[1:T].unsqueeze(-2)              # (T-1, B, N, K, K'): slot k vs next slot q
+            m[:T - 1] = (eq.long() * torch.arange(1, K + 1)).max(-1).values - 1     # the last matching slot, -1 without one
+    m = m.reshape(-1)
+    e = torch.arange(E)
+    un = m < 0
+    rank = torch.cumsum(un.long(), 0) - un.long()                                  # extras are ordered by (t, b, i, k)
+    u = torch.where(un, E + rank, e - e % K + BNK + m)
+    src = torch.full((2 * E,), -1, dtype=torch.long)
+    src[u] = e
+    return u.view(T, B, N, K), src, E + int(un.sum())
+
+
+def planted_lists(T, B, N, K, n_nodes=None, seed=0, recomputed=False, keep=0.9, dup=False):
+    """Synthetic neighbour lists (T + recomputed, B, N, K) int32: slot 0 is the agent itself, the
+    other slots distinct ids below the node count (agent i's candidates are i + 1 .. i + P mod n_nodes,
+    P = min(n_nodes - 1, 64)); each step keeps each non-self slot's neighbour with probability `keep`
+    -- in a shuffled slot -- and otherwise replaces it by an id the row did not hold. dup (K >= 3): in
+    the last step every third agent's last slot repeats its slot 1, so a neighbour kept from the step
+    before matches two slots of the next list and the LAST one must win (only the last step, which
+    is nobody's current list but its own all-extras one, so the maps stay injective)."""
+    Nn = N if n_nodes is None else n_nodes
+    P = min(Nn - 1, 64)
+    assert Nn >= N and (K == 1 or P >= 2 * (K - 1)), "not enough candidates to replace every slot"
+    g = torch.Generator().manual_seed(seed)
+    Tg = T + int(recomputed)
+    me = torch.arange(N).view(1, N, 1).expand(B, N, 1)
+    out = torch.empty(Tg, B, N, K, dtype=torch.int32)
+    held = None                                                     # (B, N, P) bool: offsets in the row
+    for t in range(Tg):
+        score = torch.rand(B, N, P, generator=g)
+        if held is not None:
+            drop = held & (torch.rand(B, N, P, generator=g) >= keep)
+            score = torch.where(held & ~drop, score - 2.0, score)   # kept neighbours stay
+            score = torch.where(drop, score + 2.0, score)           # replaced ones leave the row
+        off = score.argsort(-1)[..., :K - 1]                        # K - 1 distinct offsets, in random order
+        held = torch.zeros(B, N, P, dtype=torch.bool).scatter_(-1, off, True)
+        out[t] = torch.cat([me, (me + 1 + off) % Nn], -1).to(torch.int32)
+    if dup:
+        assert K >= 3 and T >= 2 and not recomputed
+        out[T - 1, :, 0::3, K - 1] = out[T - 1, :, 0::3, 1]
+    return out.contiguous()
+
+
+# (T, B, N, K, node count): every K at (3, 2, 50); rows T B N around a 256-row block; no next step;
+# the (T-1) B N = 400 and B N K boundaries inside blocks
+MATCH_CASES = [(3, 2, 50, K, 50, False) for K in (1, 2, 5, 8, 12, 16)] + \
+              [(1, 1, 1, 12, 64, False), (1, 3, 85, 12, 85, False), (2, 1, 128, 5, 128, False), (1, 1, 257, 3, 257, False),
+               (1, 2, 40, 12, 40, False), (3, 1, 200, 12, 200, False),
+               # duplicate ids in the last list: first match and last match differ (reuse mode only)
+               (3, 2, 50, 6, 50, True)]
+MATCH_BIG = (3, 1, 174850, 2, 174850, False)         # 2,050 blocks: block_sum_prefix's second trip; 1.05 M slots
+
+
+def match_case_id(c):
+    return "T{}-B{}-N{}-K{}".format(*c[:4]) + ("-dup" if c[5] else "")
+
+
+@functools.lru_cache(maxsize=None)
+def match_case(case, recomputed):
+    """(idx, the reference's map1, src, nev) of a planted-list case; the loop-free reference (the big
+    case could not afford the loop)."""
+    T, B, N, K, Nn, dup = case
+    idx = planted_lists(T, B, N, K, n_nodes=Nn, seed=31 + K + N, recomputed=recomputed, dup=dup and not recomputed)
+    return (idx,) + tuple(match_reference_fast(idx, T, recomputed=recomputed))

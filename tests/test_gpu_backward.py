@@ -204,6 +204,22 @@ def test_full_step_grad_matches_oracle(bptt, reuse, T, prec):
     assert abs(float(stats["loss_total"]) - stats_o["loss_total"]) <= tf * abs(stats_o["loss_total"]) + 1e-6
 
 
+def test_full_step_grad_matches_oracle_top_k16_bf16():
+    """The same at top_k = 16 (N = 40 > K, every slot of the 16-slot tiles live) in bf16."""
+    from macbf_gnn_amd.engine.oracle_engine import OracleEngine
+    tr = _trainer(DEV, N=40, bptt=True, reuse_nbr_idx=True, T=5, dtype="bf16", top_k=16)
+    assert tr.engine.K == 16
+    _round_params(tr)
+    s0, g, _ = tr.sample()
+    stats = tr.engine.step(s0, g)
+    g_hip = tr.fp.grad.clone()
+    with O.emulate_bf16(True):
+        stats_o = OracleEngine(tr).step(s0, g, forced=tr.engine.trajectory(int(float(stats["T"]))))
+    g_ref = tr.fp.grad.clone()
+    _cmp_tensors(tr, g_hip, g_ref, TOL_STEP)
+    assert abs(float(stats["loss_total"]) - stats_o["loss_total"]) <= TOL_FWD * abs(stats_o["loss_total"]) + 1e-6
+
+
 @pytest.mark.parametrize("T", [4, 12])
 def test_full_step_deterministic(T):
     tr = _trainer(DEV, N=64, B=3, T=T)

@@ -9,6 +9,7 @@ from macbf_gnn_amd import oracle as O
 from macbf_gnn_amd.ops import native
 from macbf_gnn_amd.ops.dedup import match_reference
 
+import dedup_ref as DR
 from test_gpu_backward import _cmp, _states, _trainer
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +34,32 @@ def test_cbf_match_equals_reference(recomputed):
     assert torch.equal(src[:n_ref].cpu().long(), s_ref[:n_ref])
     if not recomputed:
         assert n_ref > E            # the states move: some neighbour sets change
+
+
+@pytest.mark.parametrize("recomputed", [False, True])
+@pytest.mark.parametrize("case", DR.MATCH_CASES + [DR.MATCH_BIG], ids=DR.match_case_id)
+def test_cbf_match_on_planted_lists(case, recomputed):
+    """cbf_match on synthetic lists (tests/dedup_ref.planted_lists: self in slot 0, distinct ids, 0.9
+    of the neighbours kept per step in shuffled slots) at every K, at row counts around a 256-row
+    block, without a next step, with the step boundaries inside blocks, and above 2,048 blocks (the
+    second trip of block_sum_prefix's unrolled loop): nev, map1 and src[:nev] exact, src[nev:]
+    untouched."""
+    T, B, N, K = case[:4]
+    idx, m_ref, s_ref, n_ref = DR.match_case(case, recomputed)
+    E = T * B * N * K
+    map1 = torch.full((T, B, N, K), -7, dtype=torch.int32, device=DEV)
+    src = torch.full((2 * E,), -7, dtype=torch.int32, device=DEV)
+    cnt = torch.zeros((T * B * N + native.MATCH_BLOCK - 1) // native.MATCH_BLOCK, dtype=torch.int32, device=DEV)
+    nev = native.cbf_match(idx.to(DEV), T, map1, src, cnt, recomputed=recomputed)
+    torch.cuda.synchronize()
+    assert int(nev) == n_ref
+    assert torch.equal(map1.cpu().long(), m_ref)
+    assert torch.equal(src[:n_ref].cpu().long(), s_ref[:n_ref])
+    assert bool((src[n_ref:] == -7).all())
+    if case == DR.MATCH_BIG:
+        assert cnt.numel() > 2048
+    if K >= 2 and T >= 2 and not recomputed:      # (recomputed lists match slot k with slot k: the last step's slots alone)
+        assert n_ref > E + B * N * K, "the extras are all in the last step"
 
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])

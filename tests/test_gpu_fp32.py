@@ -348,6 +348,29 @@ def test_full_step_grad_fp32(bptt, reuse, N, extra):
     assert abs(float(stats["loss_total"]) - stats_o["loss_total"]) <= 1e-4 * abs(stats_o["loss_total"]) + 1e-6
 
 
+@pytest.mark.parametrize("top_k,reuse,N,B,fused", [(8, True, 40, 2, False), (8, False, 40, 2, False), (16, True, 40, 2, False),
+                                                   (8, True, 64, 4, True)])
+def test_full_step_grad_fp32_other_top_k(top_k, reuse, N, B, fused, monkeypatch):
+    """test_full_step_grad_fp32 at top_k = 8 / 16 with N > K (T = 5), the oracle replaying the engine's
+    trajectory: the 32x32x16 edge backward (K != 12 has no 16x16x32 kernel), cbf_match / cbf_hfwd /
+    cbf_dh / cbf_compact, the CBF backward's record decode, rev_csr and node_reduce at K != 12, per
+    parameter tensor <= 1e-3. One case runs the fused ctrl_bwd_step (MACBF_BWD_FUSED=1, 256 agents)."""
+    from macbf_gnn_amd.engine.oracle_engine import OracleEngine
+    if fused:
+        monkeypatch.setenv("MACBF_BWD_FUSED", "1")
+    tr = _trainer(bptt=True, reuse_nbr_idx=reuse, N=N, B=B, top_k=top_k)
+    assert tr.engine.K == top_k
+    assert native.bwd_step_fused(B * N, DEV) == fused and (not fused or tr.engine.nb_node == tr.engine.nb_edge)
+    s0, g, obs = tr.sample()
+    stats = tr.engine.step(s0, g, obs)
+    g_hip = tr.fp.grad.clone()
+    stats_o = OracleEngine(tr).step(s0, g, obs, forced=tr.engine.trajectory(int(float(stats["T"]))))
+    g_ref = tr.fp.grad.clone()
+    worst = sorted(((_rel(g_hip[o:o + n], g_ref[o:o + n]), pn) for m, pn, shape, o, n in tr.fp.specs), reverse=True)
+    assert worst[0][0] <= 1e-3, worst[:4]
+    assert abs(float(stats["loss_total"]) - stats_o["loss_total"]) <= 1e-4 * abs(stats_o["loss_total"]) + 1e-6
+
+
 def test_module_api_fp32_default():
     """models.CBF / models.Controller on the device default to the fp32-accurate kernels."""
     torch.manual_seed(5)

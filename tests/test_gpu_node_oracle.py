@@ -162,12 +162,12 @@ def test_x3_node_bwd_matches_fp64_oracle(name, body, chunk, k16):
     _check_x3(out, _reference(case, "fp32"), f"{name} {body}")
 
 
-def _scene_edge(case, prec):
-    """Edge-backward arguments of the case's scene: kNN graph of its states, argmax slots of a
-    ctrl_fwd on them."""
+def _scene_edge(case, prec, K=None):
+    """Edge-backward arguments of the case's scene: kNN graph of its states (K neighbours, default
+    min(N, TOP_K)), argmax slots of a ctrl_fwd on them."""
     fp, pw, _ = _nets(case["D"], prec)
     B, N, D = case["B"], case["N"], case["D"]
-    K, W = min(N, C.TOP_K), native.rec_width(D)
+    K, W = min(N, C.TOP_K) if K is None else K, native.rec_width(D)
     s = case["s"].to(DEV)
     S = native.to_records(s).contiguous()
     idx = _knn(s, K, D)
