@@ -10,7 +10,9 @@
 //   cell_sort (every resort_every steps) + scan, ctrl_fwd
 //   [copy stream] per-env goal-distance sums -> pinned host memory
 // and checks the early-stop criterion one step late (never stalls the queue on the step just
-// issued). Per-env done masks are applied on the device afterwards (rollout_stats).
+// issued). From the step at which the previous rollout ended, the check moves in front of the
+// controller step instead (run(): the zero-lag check), so the step past the horizon is not issued.
+// Per-env done masks are applied on the device afterwards (rollout_stats).
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 #include <hip/hip_runtime.h>
@@ -113,9 +115,28 @@ class RolloutDriver {
       ++gen_;      // the per-step counters are zero: set at allocation, re-armed by the last workgroup
       hd = pub_host_;
     }
+    // Zero-lag check from the expected horizon (exp_T_: where the previous rollout ended; a hint --
+    // T, tail and every buffer are the same with any value): from step exp_T_ on the publication of
+    // step t-1 is awaited after scan(t) -- the tail scan if the rollout ends here -- and BEFORE
+    // ctrl(t), so the controller step past the horizon, which nothing reads, is not issued. The
+    // sums of step t-1 arrive while the GPU runs scan(t). Earlier steps keep the lagged check.
+    const bool zero_lag = pub && zero_lag_ && check_ == 1 && !overlap_ && exp_T_ > 0;
+    ctrl_issued_ = 0;
     for (int t = 0; t < Tmax_; ++t) {
       scan_step(t, st);
+      // zero-lag: the check of step t-1 comes here, before ctrl(t), instead of after it below
+      const bool early = zero_lag && t >= 1 && t >= exp_T_;
+      if (early) {
+        wait_published(t - 1, st);
+        const int Tf = first_done(hd, t - 1);
+        if (Tf > 0) {      // scan(t) was the tail scan; ctrl(t) is not issued
+          T = Tf;
+          tail = true;
+          break;
+        }
+      }
       ctrl_step(t, st, pub);
+      ++ctrl_issued_;
       // ONE marker per step on the compute queue (each marker stalls the queue behind it for
       // ~6 us: the next dispatch waits for its completion signal); both side queues wait on it
       if (overlap_ || (early_stop && !pub)) chk(hipEventRecord(ev_main_, st), "hipEventRecord");
@@ -134,7 +155,7 @@ class RolloutDriver {
         }
         // host check every check_every steps (small scenes: a step's kernels take less than
         // the host round trip, so checking every step would leave the GPU idle)
-        if (t >= 1 && (t % check_ == 0)) {
+        if (!early && t >= 1 && (t % check_ == 0)) {
           if (pub) wait_published(t - 1, st);
           else chk(hipEventSynchronize(ev_copy_[t - 1]), "hipEventSynchronize");
           const int Tf = first_done(hd, t - 1);
@@ -167,8 +188,16 @@ class RolloutDriver {
       chk(hipEventRecord(ev_side_, hs), "hipEventRecord");     // join the side stream
       chk(hipStreamWaitEvent(st, ev_side_, 0), "hipStreamWaitEvent");
     }
+    if (pub) exp_T_ = T;  // the next rollout's expected horizon
     return {T, tail};     // converted to a tuple after the GIL is re-acquired
   }
+
+  // The zero-lag check (run()): the expected horizon (0: none; run() sets it to the horizon it found),
+  // the switch, and the controller steps the last run() issued.
+  void set_expected_horizon(int T) { exp_T_ = T < 0 ? 0 : T; }
+  int expected_horizon() const { return exp_T_; }
+  void set_zero_lag(bool on) { zero_lag_ = on; }
+  int ctrl_issued() const { return ctrl_issued_; }
 
   // Executable graphs of the post-rollout work per horizon (index T; 0: none), captured by the
   // engine (hip_engine.py _capture_bwd): run_small(..., launch_graph) launches graph T as soon as
@@ -322,6 +351,9 @@ class RolloutDriver {
   mb::CbfFwdArgs hfwd_;       // over the whole buffers (overlap_ only)
   int Tmax_, num_cu_, prec_, resort_, hfwd_blocks_, check_, publish_, poll_query_ms_, small_apw_, knn_tail_;
   bool overlap_ = false;
+  bool zero_lag_ = true;      // the zero-lag early-stop check from the expected horizon (run())
+  int exp_T_ = 0;             // horizon of the previous published early-stop run() (0: none yet)
+  int ctrl_issued_ = 0;       // controller steps issued by the last run()
   float done_thr_;
   unsigned gen_ = 0;
   unsigned long long* host_dist_;            // pinned [Tmax][B]: the copied per-env sums
@@ -732,6 +764,10 @@ void register_runtime(py::module& m) {
   py::class_<RolloutDriver>(m, "RolloutDriver")
       .def(py::init<py::dict>())
       .def("set_bwd_graphs", &RolloutDriver::set_bwd_graphs, py::arg("execs"))
+      .def("set_expected_horizon", &RolloutDriver::set_expected_horizon, py::arg("T"))
+      .def("set_zero_lag", &RolloutDriver::set_zero_lag, py::arg("on"))
+      .def_property_readonly("expected_horizon", &RolloutDriver::expected_horizon)
+      .def_property_readonly("ctrl_issued", &RolloutDriver::ctrl_issued)
       .def("run_small", &RolloutDriver::run_small, py::arg("stream"), py::arg("early_stop"),
            py::arg("launch_graph") = false, py::arg("s0") = 0, py::arg("g0") = 0,
            py::call_guard<py::gil_scoped_release>())

@@ -72,6 +72,9 @@ class HipEngine:
                               # step at >= 16K agents per rank, up to every 4th for small scenes)
     reduce_late = 0           # >0: dS steps reduced before the BPTT starts, the rest on the aux stream
                               # during it (A/B on MI355X: neutral-to-slower, 7.63 vs 7.66 ms; off)
+    expect_horizon = True     # native per-step rollout: from the step at which the previous rollout
+                              # ended, the early stop is checked before the controller step is issued
+                              # (csrc/runtime.cpp run(); a hint -- results do not depend on it)
     small_rollout = True      # envs of <= native.SMALL_MAXN graph nodes: the whole rollout is ONE
                               # persistent launch (one workgroup per env, device-side early stop)
     bwd_graph = True          # small scenes (the persistent rollout's <= 64-node envs): everything after
@@ -458,8 +461,10 @@ class HipEngine:
                 self._launched_T = T if launched else None
                 return self._tail_scan(T, tail_scanned)
             # the per-step launch loop in C++ (csrc/runtime.cpp): same launches, same order
-            T, tail_scanned = self._driver().run(cur.cuda_stream, self.hstream.cuda_stream if overlap else 0,
-                                                 self.copy_stream.cuda_stream, bool(early_stop))
+            drv = self._driver()
+            drv.set_zero_lag(bool(self.expect_horizon))       # read at each rollout, like the other switches
+            T, tail_scanned = drv.run(cur.cuda_stream, self.hstream.cuda_stream if overlap else 0,
+                                      self.copy_stream.cuda_stream, bool(early_stop))
             return self._tail_scan(T, tail_scanned)
         if overlap:
             self.hstream.wait_stream(cur)
